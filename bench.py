@@ -15,16 +15,28 @@ samples) for every channel: decimator -> discriminator -> stereo PLL/blend
 -> 32 kHz audio -> RDS bits + block sync, plus the per-block RF level
 (computeSignalLevel, main.cpp:1167) -- fmx_process_block.  All step inputs
 are generated into HBM before the timed region (fresh, phase-continuous IQ
-for every step), so `value` excludes PCIe.
+for every step), so `value` excludes PCIe.  Up to --iq-bytes of IQ stay
+resident (160 GiB: 512 blocks of 4096 channels); a run of more steps reads
+the resident blocks round and round (`config.iq_blocks_resident`), with one
+phase jump in the signal per lap.
 
 Multi-GPU: one process per GPU.  `python bench.py --gpus N` with no
 WORLD_SIZE in the environment re-launches itself under
 torch.distributed.run (N ranks, 127.0.0.1) before touching the GPU; under a
 launcher WORLD_SIZE must equal --gpus.  Channels are sharded by rank with no
 data-path collective; RCCL carries only the barrier, the max-over-ranks time,
-the summed channel count and the scan line's RF-level all_gather (the three
+the summed channel count and, with --full, the scan line's RF-level all_gather (the three
 last timed blocks of every channel are the scan's 3 reads per point,
 main.cpp:1064-1121).
+
+A plain run sets up, warms up, times --steps steps and prints the result line;
+its per-kernel and roofline figures come from HIP events inside the timed
+steps and cost no run of their own.  --full adds what takes time of its own:
+the CPU baseline (the oracle on the host cores, `cpu_baseline`) and the scan
+line with its gather (`scan`); both are null in a plain run's line.
+--dump-outputs DIR writes the last timed step's outputs (the fields of its
+fmx_block_out) as DIR/<name>.npy; the inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 
 Prints ONE JSON line (rank 0).
 """
@@ -95,8 +107,18 @@ def parse(argv=None):
     ap.add_argument("--channels", type=int, default=None, help="channels per GPU (cfg3 default 4096)")
     ap.add_argument("--total-channels", type=int, default=None, help="channels in total, sharded over ranks")
     ap.add_argument("--block", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target wall time of the all-core CPU sample")
+    ap.add_argument("--iq-bytes", type=int, default=160 << 30,
+                    help="HBM for the resident IQ of one rank (default 160 GiB: 512 blocks of 4096 channels); "
+                         "runs with more steps than fit go round the resident blocks again")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (oracle on the "
+                         "host cores) and the scan line with its RF-level gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (what a caller of "
+                         "fmx_process_block receives) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+                    help="with --full: target wall time of the all-core CPU sample")
     ap.add_argument("--retune-per-step", action="store_true",
                     help="diagnostic: fmx_retune one channel before every step (main.cpp:1028-1042)")
     ap.add_argument("--sync-steps", action="store_true",
@@ -152,6 +174,14 @@ def plan_channels(args, world, rank):
         return b, e - b, total, "strong"
     c = args.channels or 4096
     return rank * c, c, c * world, "weak"
+
+
+def iq_blocks(nblk, channels, n_iq, budget):
+    """Blocks of u8 IQ kept resident per channel: all nblk (warmup + steps)
+    while they fit in `budget` bytes over the channels, else as many as fit
+    (at least 3, the depth of the pipeline); step b then reads block
+    b % iq_blocks."""
+    return max(1, min(nblk, max(3, int(budget) // (channels * 2 * n_iq))))
 
 
 def tag_key(path):
@@ -259,6 +289,51 @@ def cpu_baseline(fmx, d_iq, C, nblk, n_iq, B, seconds):
             **{k: info[k] for k in ("cpu_model", "nproc", "affinity", "cgroup_cpus")}}
 
 
+DUMP_PCM_BYTES = 56 << 20  # pcm_l + pcm_r together; the per-channel records add < 1 MB per 4096 channels
+
+
+def dump_outputs(path, rank, out):
+    """Write the last timed step's outputs, as its fmx_block_out handed them
+    to the caller, to path/<name>.npy (ranks > 0: <name>.rank<r>.npy) in
+    float32 / float64.  `out` maps the block's fields to their device tensors.
+    What the call leaves undefined is zeroed: PCM columns from pcm_count on,
+    group slots from group_count on, the padding of fmx_rds_group.  Over
+    DUMP_PCM_BYTES of PCM, a fixed seeded sample of the channels is written
+    (pcm_channels holds their indices)."""
+    import numpy as np
+    host = {k: v.cpu().numpy() for k, v in out.items() if k not in ("pcm_l", "pcm_r")}
+    cnt = host["pcm_count"]
+    C = cnt.shape[0]
+    width = max(1, min(int(cnt.max()), out["pcm_l"].shape[1]))
+    keep = min(C, max(1, DUMP_PCM_BYTES // (2 * 4 * width)))
+    chans = np.arange(C) if keep == C else np.sort(np.random.default_rng(0).choice(C, keep, replace=False))
+    arrays = {"pcm_channels": chans.astype(np.float64)}
+    live = np.arange(width)[None, :] < cnt[chans, None]
+    for k in ("pcm_l", "pcm_r"):
+        rows = out[k] if keep == C else out[k][chans.tolist()]
+        arrays[k] = np.where(live, rows[:, :width].cpu().numpy(), np.float32(0.0))
+    for k in ("pcm_count", "stereo", "pilot_tenths", "stereo_indicator", "group_count"):
+        arrays[k] = host[k].astype(np.float64)
+    arrays["clip_ratio"] = host["clip_ratio"]
+    # fmx_rds_group as four 32-bit words: a | b << 16, c | d << 16, errors in
+    # the low byte of the third, block_index
+    w = host["groups"].astype(np.int64) & 0xFFFFFFFF
+    g = np.stack([w[..., 0] & 0xFFFF, w[..., 0] >> 16, w[..., 1] & 0xFFFF, w[..., 1] >> 16,
+                  w[..., 2] & 0xFF, w[..., 3]], axis=-1).astype(np.float64)
+    g[np.arange(g.shape[1])[None, :] >= host["group_count"][:, None]] = 0.0
+    arrays["groups"] = g  # [C][slot][a, b, c, d, errors, block_index]
+    if "signal" in host:
+        # fmx_signal_level: two floats, then four doubles
+        s = host["signal"]
+        arrays["signal"] = np.concatenate([s[:, :2].astype(np.float64),
+                                           np.ascontiguousarray(s[:, 2:]).view(np.float64)], axis=1)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"dump_outputs: {k} is {a.dtype}")
+        np.save(os.path.join(path, k + (".npy" if rank == 0 else f".rank{rank}.npy")), a)
+
+
 def _sha16(path):
     """First 16 hex digits of a file's SHA-256 (the bench line's library record)."""
     import hashlib
@@ -327,16 +402,20 @@ def main():
     h = fmx.Handle(cfg, C, device=gpu)
     # ---- inputs: synthetic stereo + RDS IQ for every step, resident in HBM ----
     n_iq = B * M
-    n_bits = int((nblk * n_iq + 2 * 2_400_000) * 1187.5 / 2.4e6) + 208  # covers the per-channel RDS offset
+    # every step reads fresh IQ while all of it fits in --iq-bytes of HBM (the
+    # default run does: 105 blocks, 35 GB); a longer run goes round the
+    # resident blocks again, with one phase jump per lap
+    nres = iq_blocks(nblk, C, n_iq, args.iq_bytes)
+    n_bits = int((nres * n_iq + 2 * 2_400_000) * 1187.5 / 2.4e6) + 208  # covers the per-channel RDS offset
     # carrier levels spread over 24 dB (0.8 .. 0.05 of full scale, seeded per
     # channel): the scan line's RF levels span the 120-point scale instead of
     # saturating it; every channel still carries stereo + RDS
     scfg = fmx.make_synth(iq_rate=2_400_000, kind=2, n_bits=n_bits, level_spread_db=24.0)
     bits, _ = fmx.synth_rds_bits(scfg, ch0, C)
     d_bits = torch.from_numpy(bits).to(dev)
-    row = 2 * n_iq * nblk
+    row = 2 * n_iq * nres
     d_iq = torch.empty((C, row), dtype=torch.uint8, device=dev)
-    h.synth_device(scfg, ch0, C, 0, n_iq * nblk, d_bits.data_ptr(), d_iq.data_ptr(), row)
+    h.synth_device(scfg, ch0, C, 0, n_iq * nres, d_bits.data_ptr(), d_iq.data_ptr(), row)
     h.sync()  # the synth (the handle's stream) has read d_bits before torch may reuse its memory
     del d_bits
     # ---- outputs ----
@@ -362,7 +441,7 @@ def main():
     def step(b):
         if args.retune_per_step:  # diagnostic A/B: a live receiver retuning one channel per block
             h.retune((b * 7919) % C, -1)
-        h.process_block(d_iq.data_ptr() + b * 2 * n_iq, row, B, outs[b % 3])
+        h.process_block(d_iq.data_ptr() + (b % nres) * 2 * n_iq, row, B, outs[b % 3])
         if args.sync_steps:
             h.sync()
 
@@ -422,16 +501,24 @@ def main():
     iq_samples = chans_all * args.steps * n_iq
     value = iq_samples / elapsed / 1e6  # MS/s, whole job
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs:
+        last = {"pcm_l": pl, "pcm_r": pr, "pcm_count": cnt, "stereo": st, "pilot_tenths": pil,
+                "stereo_indicator": ind, "clip_ratio": clip, "groups": grp, "group_count": gcnt}
+        if not args.no_signal_level:
+            last["signal"] = sig[(nblk - 1) % 3]
+        dump_outputs(args.dump_outputs, rank, last)
 
-    # ---- multi-channel scan line: every channel is a scan point; its level is
-    # the mean of the last three blocks' computeSignalLevel (main.cpp:1078-1103),
-    # gathered from all ranks (RCCL all_gather, fmx_dist.gather_levels) ----
-    level_sum = (sig[0, :, 0] + sig[1, :, 0] + sig[2, :, 0]).to(torch.float64)
-    tg0 = time.perf_counter()
-    all_levels = fmx_dist.gather_levels(level_sum.to(cdev))
-    gather_ms = (time.perf_counter() - tg0) * 1e3
+    # ---- multi-channel scan line (--full): every channel is a scan point; its
+    # level is the mean of the last three blocks' computeSignalLevel
+    # (main.cpp:1078-1103), gathered from all ranks (RCCL all_gather,
+    # fmx_dist.gather_levels) ----
     scan = None
-    if rank == 0:
+    if args.full:
+        level_sum = (sig[0, :, 0] + sig[1, :, 0] + sig[2, :, 0]).to(torch.float64)
+        tg0 = time.perf_counter()
+        all_levels = fmx_dist.gather_levels(level_sum.to(cdev))
+        gather_ms = (time.perf_counter() - tg0) * 1e3
+    if args.full and rank == 0:
         lv = all_levels.cpu().numpy()
         freq = 87_500 + 50 * np.arange(lv.size, dtype=np.int64)  # synthetic channel plan, 50 kHz raster
         line = fmx.xdr_scan_line(freq.astype(np.int32), lv, np.full(lv.size, 3, np.int32))
@@ -546,10 +633,10 @@ def main():
             ent["pmc_over_design"] = round(pb / (bpi * units), 3)
         kern[k] = ent
 
-    # ---- CPU baseline: the oracle on this box's host cores (rank 0, N=1) ----
+    # ---- CPU baseline (--full): the oracle on the host's cores (rank 0, N=1) ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(fmx, d_iq, C, nblk, n_iq, B, args.cpu_seconds)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline(fmx, d_iq, C, nres, n_iq, B, args.cpu_seconds)
 
     wl = {"cfg3": "cfg3: 4096 ch x 2.4 MS/s stereo FM + 57 kHz RDS per GPU",
           "cfg4": "cfg4: 16384 ch x 2.4 MS/s stereo FM + 57 kHz RDS sharded over the GPUs"}[args.workload]
@@ -571,7 +658,7 @@ def main():
         "config": {"workload": wl + ", M=10 -> 240 kHz, dsp_block=4096, deemphasis 50 us",
                    "total_channels": int(chans_all), "channels_rank0": C, "block": B, "iq_rate": 2_400_000,
                    "parallelism": f"channels/{world}gpu", "backend": backend if world > 1 else None,
-                   "world_reported": world_reported,
+                   "world_reported": world_reported, "iq_blocks_resident": nres,
                    **({"retune_per_step": True} if args.retune_per_step else {})},
         "per_gpu_ms_s": round(value / world, 1),
         "realtime_channels_per_gpu": round(value / world / 2.4, 1),

@@ -25,7 +25,7 @@ def test_two_ranks_on_one_gpu_shard_time_and_gather(torch_cuda):
         env.pop(k, None)
     env["FMX_BENCH_BACKEND"] = "gloo"
     total = 4096
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--total-channels", str(total)], capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

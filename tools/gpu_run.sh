@@ -4,8 +4,8 @@
 # (no further GPU step runs).  Test failures (pytest rc 1) do not.
 #   tools/gpu_run.sh TAG step [step ...]
 # steps: tests (pytest -m gpu), ptests (pipelined parity only), smoke,
-#        bench (driver-shaped: --steps 20 --warmup 5), benchfull (default
-#        bench with the CPU baseline), trace (rocprofv3 kernel trace + gaps),
+#        bench (driver-shaped: --steps 20 --warmup 5), benchfull (bench.py
+#        --full: with the CPU baseline), trace (rocprofv3 kernel trace + gaps),
 #        stats (rocprofv3 --kernel-trace --stats), pmc (FETCH / WRITE passes),
 #        ubench (tools/ubench/chainlat), sweep (channel sweep), stamps (stage clocks,
 #        diagnostics library), iso (isolated kernel times, diagnostics library),
@@ -40,7 +40,7 @@ for step in "$@"; do
       timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$TAG.json 2> $O/bench_$TAG.err; rc=$?
       python3 -c "import json,sys; r=json.load(open('$O/bench_$TAG.json')); print(r['value'], r['ms_per_step'], {k: v['avg_ms'] for k, v in r['kernels'].items()}, r['host_submit_ms'])" ;;
     benchfull)
-      timeout -k 10 400 python bench.py > $O/benchfull_$TAG.json 2> $O/benchfull_$TAG.err; rc=$?
+      timeout -k 10 400 python bench.py --full > $O/benchfull_$TAG.json 2> $O/benchfull_$TAG.err; rc=$?
       python3 -c "import json,sys; r=json.load(open('$O/benchfull_$TAG.json')); print(r['value'], r['ms_per_step'], r['cpu_baseline']['value'] if r['cpu_baseline'] else None)" ;;
     trace)
       bash tools/gpu_trace.sh trace_$TAG > $O/trace_$TAG.log 2>&1; rc=$?

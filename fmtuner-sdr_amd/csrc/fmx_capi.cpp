@@ -1852,6 +1852,27 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
     if (d_group_count) HIP_TRY(hipMemsetAsync(d_group_count, 0, sizeof(int) * h->C, h->sA));
     return FMX_OK;
   }
+  // A stage call does not advance h->step, so consecutive fmx_rds calls use
+  // one slot, and the front end below writes this call's `count` RDS-rate
+  // samples over row[0 .. count) of the previous call's -- the row k_rds's
+  // ring refill (a.in_prev) reads when a short call (count < 256) follows a
+  // checkpointed one (count_prev >= 256).  That overlap cannot reach the
+  // ring: rds_ring_fill rewrites all 256 entries from row[count_prev - 256 ..
+  // count_prev), then the call's own stores (behind the s_waitcnt) replace
+  // the oldest `count` of them, so what stays is row[count_prev - 256 + count
+  // .. count_prev), and count_prev - 256 + count >= count for every
+  // checkpointed call.  Nothing reads the ring in between: the rebuild after
+  // a reset does, but k_reset runs from prepare(), before this front end,
+  // refills from the intact row and sets ring_ok.
+  // (tests/test_gpu_rds_ring.py, test_ring_refill_previous_call_barely_long.)
+  // NOT covered by that argument, and untested: a checkpointed fmx_rds call,
+  // fmx_reset of a few channels (the list path), then fmx_process_block on
+  // the generic front end.  step has not advanced, so process_block's front
+  // end writes its RDS-rate samples into this same slot on sA, and the
+  // RSP_RDS reset part runs on sC behind it: k_reset would refill from the
+  // overwritten row and rebuild from wrong samples (a wrong result, not a
+  // fault).  With k_rs (the k_fe8 path) the reset part runs before the row is
+  // written.
   const int buf = static_cast<int>(h->step % FMX_NBUF);
   if ((rc = tset_advance(h, h->t_rds, n, static_cast<int>(h->step % FMX_SSLOTS), h->sA, nullptr)) != FMX_OK) return rc;
   {

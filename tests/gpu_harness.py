@@ -9,7 +9,8 @@ def run_gpu_pipeline(fmx, torch, cfg, iq, nblk, n=None, resets=None, params=None
     resets {block: channel}, retunes {block: (channel, mute_samples)},
     params {block: [(key, value, channel)]} are applied before that block.
     ktimes (a dict): filled with fmx_kernel_times ({kernel: (ms, launches)})
-    of the whole run."""
+    of the whole run.  Each block's "group_block_index" holds the
+    block_index field of every record in "groups"."""
     C = iq.shape[0]
     B = cfg.block
     M = cfg.iq_rate // cfg.dsp_rate
@@ -48,19 +49,21 @@ def run_gpu_pipeline(fmx, torch, cfg, iq, nblk, n=None, resets=None, params=None
         h.sync()
         g = grp.cpu().numpy().view(np.uint8).reshape(C, GS, 16)
         gc = gcnt.cpu().numpy()
-        groups = []
+        groups, gblocks = [], []
         for c in range(C):
-            lst = []
+            lst, bl = [], []
             for k in range(min(int(gc[c]), GS)):
                 w = g[c, k]
                 a, bb, cc, d = np.frombuffer(w[:8].tobytes(), dtype=np.uint16)
                 lst.append((int(a), int(bb), int(cc), int(d), int(w[8])))
+                bl.append(int(np.frombuffer(w[12:16].tobytes(), dtype=np.uint32)[0]))
             groups.append(lst)
+            gblocks.append(bl)
         res.append(dict(mpx=mpx[:, :n].cpu().numpy().copy(), pcm_l=pl.cpu().numpy().copy(),
                         pcm_r=pr.cpu().numpy().copy(), count=cnt.cpu().numpy().copy(),
                         stereo=st.cpu().numpy().copy(), pilot=pil.cpu().numpy().copy(),
                         clip=clip.cpu().numpy().copy(), indicator=ind.cpu().numpy().copy(),
-                        groups=groups))
+                        groups=groups, group_block_index=gblocks))
     if ktimes is not None:
         ktimes.update(h.kernel_times())
     h.close()

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import gpu_harness as H
+import rds_wave as W
 from test_gpu_parity import make_iq
 
 pytestmark = pytest.mark.gpu
@@ -143,3 +144,142 @@ def test_ring_refill_short_and_long_rds_calls(fmx, torch_cuda):
         pos += n
     for h in hs:
         h.close()
+
+
+@pytest.mark.parametrize("ring_reads", ["every call", "after short calls"])
+@pytest.mark.parametrize("seq", list(W.BARELY_LONG))
+def test_ring_refill_previous_call_barely_long(fmx, oracle, torch_cuda, seq, ring_reads):
+    """fmx_rds on two handles, one writing the ring every call, through short
+    calls right after barely-long ones; after every call the rings are equal
+    (and hold samples) and the groups are equal, and the first handle's groups
+    equal the oracle's RDS stage given the same call sizes and resets, so the
+    diagnostic handle is not the only witness.
+    fmx_diag_rds_ring refills the ring of EVERY checkpointed channel from the
+    intact row and marks it valid, so with a ring read after every call k_rds's
+    own refill never runs; "after short calls" reads the rings only behind
+    calls of <= 300 samples and at the end, which leaves the refill to k_rds.
+    Consecutive fmx_rds calls share one slot, and the front end does write
+    this call's samples over row[0 .. count) of the previous call's, but of
+    the refilled entries only row[count_prev - 256 + count .. count_prev)
+    outlive the call's own ring stores, and count_prev >= 256 (the comment in
+    fmx_rds, fmx_capi.cpp)."""
+    torch = torch_cuda
+    C, fs = W.BARELY_LONG_ROWS, 240_000
+    steps = W.BARELY_LONG[seq]
+    sizes, want_resets = W.split_steps(steps, C)
+    rows = W.barely_long_rows(fs)
+    dev = torch.device("cuda")
+    d_mpx = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+    row = rows.shape[1]
+    hs = [fmx.Handle(fmx.make_config(), C), fmx.Handle(fmx.make_config(), C)]
+    hs[1].diag_set(RING_ALWAYS, 1)
+    grp = [torch.zeros((C, 8, 4), dtype=torch.int32, device=dev) for _ in hs]
+    gcnt = [torch.zeros(C, dtype=torch.int32, device=dev) for _ in hs]
+    got = [[] for _ in range(C)]  # per channel, per call
+    pos = i = 0
+    for s in steps:
+        if not isinstance(s, int):
+            for h in hs:
+                h.reset(s[1])
+            continue
+        for k, h in enumerate(hs):
+            h.rds(d_mpx.data_ptr() + 4 * pos, row, s, grp[k].data_ptr(), 8, gcnt[k].data_ptr())
+        for h in hs:
+            h.sync()
+        k0, k1 = gcnt[0].cpu().numpy(), gcnt[1].cpu().numpy()
+        g0, g1 = grp[0].cpu().numpy(), grp[1].cpu().numpy()
+        assert np.array_equal(k0, k1), (i, s)
+        for c, lst in enumerate(H._groups_of(g0, k0, 8)):
+            assert lst == H._groups_of(g1[c:c + 1], k1[c:c + 1], 8)[0], (i, s, c)
+            got[c].append(lst)
+        if ring_reads == "every call" or s <= 300 or i == len(sizes) - 1:
+            _assert_rings_equal(hs, [0, 5, 7, 11], f"call {i} (n={s})")
+        pos += s
+        i += 1
+    for h in hs:
+        h.close()
+    ngroups = 0
+    for c in range(C):
+        want = W.oracle_rds_calls(oracle, rows[c], fs, sizes=sizes, resets=want_resets[c])[0]
+        assert got[c] == want, c
+        ngroups += sum(len(x) for x in want)
+    assert ngroups >= 3
+    print(f"\nbarely long {seq} / {ring_reads}: {ngroups} groups compared with the oracle")
+
+
+@pytest.mark.parametrize("ring_reads", ["every call", "after short calls"])
+def test_ring_refill_ragged_process_block_generic_front_end(fmx, oracle, torch_cuda, ring_reads):
+    """process_block at 2.048 MS/s / 256 kHz (M = 8) with call sizes that are
+    no multiple of 4 -- the generic k_frontend path, whose k_rds is not the
+    fused one and so leaves the ring to checkpoints -- long (3001) and short
+    (333: 222 RDS-rate samples) in a ragged order, a sync after every call
+    (the refill logic only, not the streams).  A reset of channel 3 before
+    call 4 (long after long: k_reset's refill shows in the rebuilt sums, that
+    is in the outputs) and of channel 7 before call 9 (short after long: 34
+    ring entries of k_reset's refill outlive the call).  Every output
+    identical between the handle that checkpoints and the one that writes the
+    ring, groups equal to the oracle pipeline's with the same sizes and
+    resets, rings equal.
+    A ring read (fmx_diag_rds_ring) refills every checkpointed channel's ring
+    and marks it valid, so read after every call it leaves neither k_rds nor
+    k_reset a refill to do; "after short calls" reads the rings only behind
+    the 333-sample calls -- where k_rds's refill, or k_reset's, must have run
+    first -- and behind the last call."""
+    torch = torch_cuda
+    C, B, M = 20, 4096, 8
+    rates = dict(iq_rate=2_048_000, dsp_rate=256_000)
+    sizes = [3001, 3001, 333, 3001] + [3001, 333, 333, 3001] * 9
+    resets = {4: 3, 9: 7}
+    assert sizes[8] == 3001 and sizes[9] == 333
+    assert len(sizes) == 40 and all(n % 4 for n in sizes)
+    iq, _ = make_iq(fmx, 2, C, 1, iq_rate=rates["iq_rate"], M=M, ch0=300, n=sum(sizes))
+    cfg = fmx.make_config(**rates)
+    dev = torch.device("cuda")
+    d_iq = torch.from_numpy(np.ascontiguousarray(iq)).to(dev)
+    hs = [fmx.Handle(cfg, C), fmx.Handle(cfg, C)]
+    hs[1].diag_set(RING_ALWAYS, 1)
+    GS = 8
+
+    def bufs():
+        f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        return dict(mpx=f(C, B), pl=f(C, B), pr=f(C, B), cnt=z(C), st=z(C), pil=z(C), clip=f(C), grp=z(C, GS, 4),
+                    gcnt=z(C), ind=z(C))
+
+    bs = [bufs(), bufs()]
+    outs = [fmx.BlockOut(b["mpx"].data_ptr(), B, b["pl"].data_ptr(), b["pr"].data_ptr(), B, b["cnt"].data_ptr(),
+                         b["st"].data_ptr(), b["pil"].data_ptr(), b["clip"].data_ptr(), b["grp"].data_ptr(), GS,
+                         b["gcnt"].data_ptr(), None, b["ind"].data_ptr()) for b in bs]
+    got = [[] for _ in range(C)]
+    pos = 0
+    for i, n in enumerate(sizes):
+        for h, o in zip(hs, outs):
+            if i in resets:
+                h.reset(resets[i])
+            h.process_block(d_iq.data_ptr() + 2 * M * pos, iq.shape[1], n, o)
+            h.sync()
+        for k in ("cnt", "st", "pil", "gcnt", "grp", "ind"):
+            a, b = bs[0][k].cpu().numpy(), bs[1][k].cpu().numpy()
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (i, k)
+        for k, w in (("mpx", n), ("pl", B), ("pr", B)):
+            a, b = bs[0][k][:, :w].cpu().numpy(), bs[1][k][:, :w].cpu().numpy()
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (i, k)
+        for c, lst in enumerate(H._groups_of(bs[0]["grp"].cpu().numpy(), bs[0]["gcnt"].cpu().numpy(), GS)):
+            got[c].append(lst)
+        if ring_reads == "every call" or n == 333 or i == len(sizes) - 1:
+            _assert_rings_equal(hs, [0, 3, 7, 8, 19], f"call {i} (n={n})")
+        pos += n
+    for h in hs:
+        h.close()
+    ngroups = 0
+    for c in (0, 3, 7, 8, 19):
+        p = oracle.Pipeline(oracle.make_cfg(**rates))
+        want, pos = [], 0
+        for i, n in enumerate(sizes):
+            if resets.get(i) == c:
+                p.reset()
+            want.append(p.block(iq[c, 2 * M * pos:2 * M * (pos + n)])["groups"])
+            pos += n
+        assert got[c] == want, c
+        ngroups += sum(len(x) for x in want)
+    assert ngroups >= 3

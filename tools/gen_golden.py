@@ -5,7 +5,12 @@
                   slips, noise) and the RDS groups the REFERENCE's own
                   BlockStream (src/redsea_port/block_sync.cpp + group.cpp,
                   compiled by oracle/Makefile into oracle/_ref/libfmx_ref.so)
-                  emits for them.  Pins the oracle's and the GPU's block sync.
+                  emits for them.  Pins the oracle's block sync
+                  (tests/test_oracle_pinning.py) and the GPU's: the streams
+                  are transmitted as waveforms (tests/rds_wave.py) and the
+                  groups fmx_rds / fmx_process_block decode must begin with
+                  these (tests/test_gpu_rds_edge_streams.py, inputs checked
+                  on the CPU by tests/test_rds_edge_streams.py).
   xdr_server.json group streams (clean, burst errors, missing blocks, PI
                   changes as retunes make them) and scan lines, with the lines
                   the REFERENCE's own XDRServer (src/xdr_server.cpp, compiled

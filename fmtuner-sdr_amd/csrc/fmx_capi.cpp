@@ -1141,7 +1141,7 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
   float *mpx = o->d_mpx ? o->d_mpx : h->mpx[buf];
   const int mpx_stride = o->d_mpx ? o->mpx_stride : h->row;
   hipEvent_t evFE = h->evF[h->step % FMX_FRING];
-  bool use_rs = false, pil_k = false;
+  bool use_rs = false, pil_k = false, rds_reset_on_a = false;
   // ---- front end (sA) ----
   {
     FeArgs a = fe_args(h, n, h->M > 1 ? FE_IN_U8_DECIM : FE_IN_U8_DIRECT, buf);
@@ -1164,7 +1164,12 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
     // k_rs takes one resampler schedule for all channels: the RDS timing set
     // is never reset per channel (SubcarrierSet::reset, subcarrier.cpp:108)
     const bool fe8 = frontend_is_fe8(a, h->M, h->hdes->dec_tpp);
-    use_rs = rds && h->hdes->rds_del <= 2.1f && h->t_rds.G == 1 && fe8;
+    // k_rs reads the MPX rows -- the caller's, when d_mpx is given -- with
+    // 16-B loads: only on a 16-B aligned base with a stride of whole 16-B
+    // groups.  Any other caller geometry keeps the resampler inside k_fe8
+    // (its RS = true instance, scalar MPX stores): correct, slower.
+    const bool mpx_vec16 = ((reinterpret_cast<uintptr_t>(mpx) | (static_cast<uintptr_t>(mpx_stride) * 4)) & 15) == 0;
+    use_rs = rds && h->hdes->rds_del <= 2.1f && h->t_rds.G == 1 && fe8 && mpx_vec16;
     // the pilot BPF of a k_fe8 step runs as k_pilot (after it, on sA): k_fe8
     // writes the MPX and the stereo history rows k_pilot starts from
     // (FMX_FE_PILOT, A/B: inside k_fe8's RS = true instance, no k_pilot)
@@ -1183,6 +1188,19 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
       a.next_sched_src = h->t_rds.h_dev[h->t_rds.spec_img];
       a.next_sched_dst = h->t_rds.d_slot[nrslot];
       a.next_sched_n16 = spec16;
+    }
+    // A stage fmx_rds call does not advance the step, so this front end may
+    // be about to write its RDS-rate samples (no k_rs) into the very slot the
+    // last RDS call left its samples in -- the row the RDS reset part refills
+    // a checkpointed ring from.  Then that part runs here, on sA ahead of the
+    // front end and behind the RDS stream's earlier work, instead of on sC
+    // behind the front end.  (With k_rs the row is written on sC, after the
+    // reset part.)
+    if (rds && !use_rs && h->rds_last_buf == buf && !h->rl_pending.empty()) {
+      HIP_TRY(hipEventRecord(h->evTmpC, h->sC));
+      HIP_TRY(hipStreamWaitEvent(h->sA, h->evTmpC, 0));
+      if ((rc = launch_reset_parts(h, RSP_RDS, h->sA)) != FMX_OK) return rc;
+      rds_reset_on_a = true;
     }
     KBind t(h, fe8 ? FMX_K_FRONTEND : FMX_K_FRONTEND_GENERIC, h->sA, evFE);
     if ((rc = launch_frontend_m(a, h->M, h->hdes->dec_tpp, h->sA, dec_warm(h))) != FMX_OK) {
@@ -1291,7 +1309,7 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
 #define FMX_RS_AFTER_PILOT 0
 #endif
   HIP_TRY(hipStreamWaitEvent(h->sC, rs_on_a ? h->evR[buf] : ((FMX_RS_AFTER_PILOT && pil_k) ? h->evP[buf] : evFE), 0));
-  if ((rc = launch_reset_parts(h, RSP_RDS, h->sC)) != FMX_OK) return rc;
+  if (!rds_reset_on_a && (rc = launch_reset_parts(h, RSP_RDS, h->sC)) != FMX_OK) return rc;
   if (rds) {
     RdsArgs a = rds_args(h, buf);
     a.groups = o->d_groups;
@@ -1865,14 +1883,14 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
   // a reset does, but k_reset runs from prepare(), before this front end,
   // refills from the intact row and sets ring_ok.
   // (tests/test_gpu_rds_ring.py, test_ring_refill_previous_call_barely_long.)
-  // NOT covered by that argument, and untested: a checkpointed fmx_rds call,
-  // fmx_reset of a few channels (the list path), then fmx_process_block on
-  // the generic front end.  step has not advanced, so process_block's front
-  // end writes its RDS-rate samples into this same slot on sA, and the
-  // RSP_RDS reset part runs on sC behind it: k_reset would refill from the
-  // overwritten row and rebuild from wrong samples (a wrong result, not a
-  // fault).  With k_rs (the k_fe8 path) the reset part runs before the row is
-  // written.
+  // A checkpointed fmx_rds call, fmx_reset of a few channels (the list path),
+  // then fmx_process_block on the generic front end: step has not advanced, so
+  // that front end writes its RDS-rate samples into this same slot on sA.
+  // process_block therefore runs the RDS reset part on sA ahead of its front
+  // end in that case (rds_last_buf == its slot, no k_rs), so the refill reads
+  // the intact row; with k_rs the reset part runs on sC before k_rs writes the
+  // row.  (tests/test_gpu_abi_geometry.py,
+  // test_checkpointed_rds_reset_then_generic_process_block.)
   const int buf = static_cast<int>(h->step % FMX_NBUF);
   if ((rc = tset_advance(h, h->t_rds, n, static_cast<int>(h->step % FMX_SSLOTS), h->sA, nullptr)) != FMX_OK) return rc;
   {

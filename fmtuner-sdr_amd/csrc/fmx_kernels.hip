@@ -557,7 +557,12 @@ __global__ __launch_bounds__(256) void k_frontend(FeArgs a) {
   const float agc_bw = (par.agc == 1) ? 0.01f : 0.001f;
   int dec_valid = 0;
   if (a.in_mode == FE_IN_U8_DECIM) dec_valid = a.dec_valid[c];
-  const uint16_t *iq16 = reinterpret_cast<const uint16_t *>(a.iq + (size_t)c * a.iq_stride);
+  // the caller's IQ row by bytes: the ABI promises no alignment, and this is
+  // the path for every row the 16-B loads (VEC, k_fe8) cannot take
+  const uint8_t *iqrow = a.iq + (size_t)c * a.iq_stride;
+  auto iq16 = [&](long g) __attribute__((always_inline)) {
+    return (uint16_t)((uint16_t)iqrow[2 * g] | ((uint16_t)iqrow[2 * g + 1] << 8));
+  };
   const uint8_t *dhist = a.dec_hist + (size_t)c * 2 * FMX_MAX_DEC;
   // RDS schedule of this channel's timing group
   const FmxSched *sched = nullptr;
@@ -649,7 +654,7 @@ __global__ __launch_bounds__(256) void k_frontend(FeArgs a) {
       if constexpr (M > 1) {
         if (want_sig)
           for (int j = tid; j < cnt * M; j += 256) {
-            const uint16_t w = iq16[(long)n0 * M + j];
+            const uint16_t w = iq16((long)n0 * M + j);
             sig.sample(w & 255u, w >> 8);
           }
         const long g0 = (long)n0 * M - (L - 1);
@@ -658,7 +663,7 @@ __global__ __launch_bounds__(256) void k_frontend(FeArgs a) {
           const long g = g0 + li;
           float fi = 0.0f, fq = 0.0f;
           if (g >= 0) {
-            const uint16_t w = iq16[g];
+            const uint16_t w = iq16(g);
             fi = (float)(w & 255) - 127.5f;
             fq = (float)(w >> 8) - 127.5f;
           } else {
@@ -903,7 +908,7 @@ __global__ __launch_bounds__(256) void k_frontend(FeArgs a) {
     for (int h = tid; h < L - 1; h += 256) {
       const long g = total - (L - 1) + h;
       uint16_t v;
-      if (g >= 0) v = iq16[g];
+      if (g >= 0) v = iq16(g);
       else {
         const int hh = (L - 1) + (int)g; // old history index
         v = (uint16_t)dhist[2 * hh] | ((uint16_t)dhist[2 * hh + 1] << 8);
@@ -2675,8 +2680,9 @@ __global__ void k_synth(fmx_synth_config cfg, uint32_t ch0, int n_ch, int64_t sa
   const uint8_t *b = bits ? bits + (size_t)ci * cfg.n_bits : nullptr;
   uint8_t iq[2];
   fmx_synth_sample(&cfg, ch, &cp, sample0 + i, b, iq);
-  uint16_t w = (uint16_t)iq[0] | ((uint16_t)iq[1] << 8);
-  reinterpret_cast<uint16_t *>(out + (size_t)ci * out_stride)[i] = w;
+  uint8_t *o = out + (size_t)ci * out_stride + 2 * (size_t)i; // by bytes: any base, any stride
+  o[0] = iq[0];
+  o[1] = iq[1];
 }
 
 /* ================================================================== */

@@ -92,6 +92,8 @@ def lib():
         "fmx_decimate": (i, [vp, vp, sz, i, vp, i]),
         "fmx_decimate_u8": (i, [vp, vp, sz, i, vp, sz]),
         "fmx_demod": (i, [vp, vp, i, i, vp, i, vp, i, vp]),
+        "fmx_demod_u8": (i, [vp, vp, sz, i, vp, i, vp, i, vp, vp]),
+        "fmx_downsample": (i, [vp, vp, i, i, vp, i, vp]),
         "fmx_stereo": (i, [vp, vp, i, i, vp, vp, i, vp, vp]),
         "fmx_afpost": (i, [vp, vp, vp, i, i, vp, vp, i, i, vp]),
         "fmx_rds": (i, [vp, vp, i, i, vp, i, vp]),
@@ -217,6 +219,15 @@ class Handle:
     def demod(self, d_iq, in_stride, n, d_mpx, mpx_stride, d_mono=None, mono_stride=0, d_count=None):
         self._ck(self.L.fmx_demod(self.h, C.c_void_p(d_iq), in_stride, n, C.c_void_p(d_mpx), mpx_stride,
                                   C.c_void_p(d_mono), mono_stride, C.c_void_p(d_count)), "fmx_demod")
+
+    def demod_u8(self, d_iq, iq_stride, n, d_mpx, mpx_stride, d_mono=None, mono_stride=0, d_count=None, d_clip=None):
+        self._ck(self.L.fmx_demod_u8(self.h, C.c_void_p(d_iq), iq_stride, n, C.c_void_p(d_mpx), mpx_stride,
+                                     C.c_void_p(d_mono), mono_stride, C.c_void_p(d_count), C.c_void_p(d_clip)),
+                 "fmx_demod_u8")
+
+    def downsample(self, d_mpx, mpx_stride, n, d_out, out_stride, d_count):
+        self._ck(self.L.fmx_downsample(self.h, C.c_void_p(d_mpx), mpx_stride, n, C.c_void_p(d_out), out_stride,
+                                       C.c_void_p(d_count)), "fmx_downsample")
 
     def stereo(self, d_mpx, mpx_stride, n, d_l, d_r, lr_stride, d_st=None, d_pilot=None):
         self._ck(self.L.fmx_stereo(self.h, C.c_void_p(d_mpx), mpx_stride, n, C.c_void_p(d_l),

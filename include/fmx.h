@@ -23,6 +23,15 @@
  *     available from fmx_last_error(); nothing throws across the ABI;
  *   - pointers named d_* are DEVICE pointers (hipMalloc'd memory on the
  *     handle's device), pointers named h_* are host pointers;
+ *   - buffer geometry: a base pointer needs its element's own alignment only
+ *     (1 for u8 IQ, 4 for float / int / fmx_rds_group, 8 for fmx_signal_level)
+ *     and a stride is any element count >= the row's logical length; a row's
+ *     cells past its logical length (MPX n, PCM pcm_count[c], groups
+ *     min(count, groups_stride)) are never written.  The fast kernels need
+ *     more and the host checks it per call: IQ base, iq_stride and 2*n*M
+ *     multiples of 16 bytes (k_fe8), MPX base 16-B aligned and mpx_stride a
+ *     multiple of 4 floats (k_rs, k_pilot's 16-B loads).  Any other geometry
+ *     is correct, on slower kernels;
  *   - a handle is not thread-safe (like the reference objects); all work is
  *     queued on the handle's own HIP stream, fmx_sync() waits for it.
  *

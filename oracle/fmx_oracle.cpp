@@ -1723,6 +1723,9 @@ size_t oracle_demod_process_split(void *p, const uint8_t *iq, float *mpx, float 
   return static_cast<ref::FMDemod *>(p)->processSplit(iq, mpx, mono, n);
 }
 float oracle_demod_clip_ratio(void *p) { return static_cast<ref::FMDemod *>(p)->clipRatio; }
+size_t oracle_demod_downsample(void *p, const float *mpx, float *audio, size_t n) {
+  return static_cast<ref::FMDemod *>(p)->downsampleAudio(mpx, audio, n);
+}
 
 void *oracle_stereo_create(int in, int out) { return new ref::StereoDecoder(in, out); }
 void oracle_stereo_destroy(void *p) { delete static_cast<ref::StereoDecoder *>(p); }

@@ -96,6 +96,8 @@ size_t oracle_demod_process_split_complex(void *p, const float *iq_cf, float *mp
 size_t oracle_demod_process_split(void *p, const uint8_t *iq, float *mpx,
                                   float *mono, size_t n);
 float oracle_demod_clip_ratio(void *p);
+/* FMDemod::downsampleAudio(demod, audio, n) (fm_demod.cpp:279-295) */
+size_t oracle_demod_downsample(void *p, const float *mpx, float *audio, size_t n);
 
 void *oracle_stereo_create(int input_rate, int output_rate);
 void oracle_stereo_destroy(void *p);

@@ -65,6 +65,7 @@ def lib():
             "oracle_demod_process_split_complex": (sz, [vp, vp, vp, vp, sz]),
             "oracle_demod_process_split": (sz, [vp, vp, vp, vp, sz]),
             "oracle_demod_clip_ratio": (C.c_float, [vp]),
+            "oracle_demod_downsample": (sz, [vp, vp, vp, sz]),
             "oracle_stereo_create": (vp, [i, i]),
             "oracle_stereo_destroy": (None, [vp]),
             "oracle_stereo_reset": (None, [vp]),

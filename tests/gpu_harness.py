@@ -286,3 +286,319 @@ def run_gpu_sampled(fmx, torch, cfg, C, scfg, nblk, keep, setup=None, retunes=No
     iq_keep = d_iq.index_select(0, kidx).cpu().numpy()
     h.close()
     return res, iq_keep, tx[keep]
+
+
+# ---- caller geometry: buffers inside larger sentinel-filled allocations ----
+SENTINEL_F32 = 0x7FC0DEAD   # a quiet NaN no kernel produces
+SENTINEL_BYTE = 0xA5        # bytes and ints (0xA5A5A5A5)
+
+
+class Guarded:
+    """A caller-owned buffer of `rows` rows of `stride` cells whose base lies
+    `off` cells inside a larger allocation filled with a sentinel (`tail`
+    more cells behind the last row).  kind: "f32", "i32" or "u8"; `cell`:
+    elements per cell (4 x i32 for a 16-byte fmx_rds_group record).  The
+    allocation itself is torch's (256-B aligned), so `off` alone sets the
+    base's alignment."""
+
+    def __init__(self, torch, kind, rows, stride, off=1, tail=21, cell=1):
+        self.kind, self.rows, self.stride, self.off, self.cell = kind, rows, stride, off, cell
+        self.ncell = off + rows * stride + tail
+        dev = torch.device("cuda")
+        if kind == "u8":
+            self.t = torch.empty(self.ncell * cell, dtype=torch.uint8, device=dev)
+            self.pat, self.raw_dtype = SENTINEL_BYTE, np.uint8
+        else:
+            self.t = torch.empty(self.ncell * cell, dtype=torch.int32, device=dev)
+            self.pat = SENTINEL_F32 if kind == "f32" else SENTINEL_BYTE * 0x01010101
+            self.raw_dtype = np.uint32
+        self.fill()
+
+    def fill(self):
+        self.t.fill_(self.pat - (1 << 32) if self.pat >= (1 << 31) else self.pat)
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr() + self.off * self.cell * self.t.element_size()
+
+    def raw(self):
+        """The whole allocation on the host, unsigned."""
+        return self.t.cpu().numpy().view(self.raw_dtype)
+
+    def view(self, raw=None, dtype=None):
+        """[rows][stride * cell] of the buffer proper (dtype: a numpy view type)."""
+        raw = self.raw() if raw is None else raw
+        v = raw[self.off * self.cell:(self.off + self.rows * self.stride) * self.cell].reshape(self.rows, -1)
+        return v if dtype is None else v.view(dtype)
+
+    def check(self, lens, tag, raw=None):
+        """Every cell outside row r's first lens[r] cells (a scalar: every
+        row's) still holds the sentinel -- before the base, between the rows'
+        logical ends and the next row, behind the last row; a float cell
+        inside holds none (it was written)."""
+        raw = self.raw() if raw is None else raw
+        lens = np.broadcast_to(np.asarray(lens, dtype=np.int64), (self.rows,))
+        assert np.all(lens >= 0) and np.all(lens <= self.stride), (tag, lens.min(), lens.max(), self.stride)
+        inside = np.zeros(self.ncell, dtype=bool)
+        col = np.arange(self.stride)
+        inside[self.off:self.off + self.rows * self.stride] = (col[None, :] < lens[:, None]).reshape(-1)
+        cellmask = np.repeat(inside, self.cell)
+        bad = np.nonzero(~cellmask & (raw != self.pat))[0]
+        assert bad.size == 0, (tag, "guard cells overwritten", bad.size,
+                               [(int(i) // self.cell - self.off) for i in bad[:8]])
+        if self.kind == "f32":
+            assert not np.any(raw[cellmask] == self.pat), (tag, "logical cells left unwritten")
+
+
+def records_to_groups(rec_u8, counts, stride):
+    """rec_u8: uint8 [C][stride * 16] fmx_rds_group records -> per channel
+    [(a, b, c, d, errors)] of its first min(count, stride) records."""
+    out = []
+    for c in range(len(counts)):
+        lst = []
+        for k in range(min(int(counts[c]), stride)):
+            w = rec_u8[c, 16 * k:16 * k + 16]
+            a, bb, cc, d = np.frombuffer(w[:8].tobytes(), dtype=np.uint16)
+            lst.append((int(a), int(bb), int(cc), int(d), int(w[8])))
+        out.append(lst)
+    return out
+
+
+def skewed_iq(torch, iq, off, pad):
+    """The rows of iq (uint8 [C][row]) on the device at byte offset `off` of
+    an allocation, `row + pad` bytes apart.  -> (tensor, base address, stride)."""
+    C, row = iq.shape
+    stride = row + pad
+    t = torch.full((off + C * stride + 64,), SENTINEL_BYTE, dtype=torch.uint8, device=torch.device("cuda"))
+    t[off:off + C * stride].view(C, stride)[:, :row] = torch.from_numpy(np.ascontiguousarray(iq)).to(t.device)
+    return t, t.data_ptr() + off, stride
+
+
+def run_gpu_geometry(fmx, torch, cfg, iq, nblk, geom, ktimes=None):
+    """run_gpu_pipeline on caller geometry: every output of fmx_process_block
+    lives in a Guarded allocation, refilled with the sentinel before each call
+    and checked after it (MPX [c][0..n), PCM [c][0..count[c]), groups
+    [c][0..min(count, stride)), the per-channel vectors [0..C)).
+    geom: mpx / pcm = (base offset, stride) in floats, grp = (offset, stride)
+    in records, iq = (byte offset, bytes added to the row).  Returns the
+    per-block dicts of run_gpu_pipeline (PCM rows cut to the stride)."""
+    C = iq.shape[0]
+    B = cfg.block
+    M = cfg.iq_rate // cfg.dsp_rate
+    n = B
+    h = fmx.Handle(cfg, C)
+    keep, iq_base, iq_stride = skewed_iq(torch, iq, *geom["iq"])
+    mo, ms = geom["mpx"]
+    po, ps = geom["pcm"]
+    go, gs = geom["grp"]
+    G = dict(mpx=Guarded(torch, "f32", C, ms, off=mo), pl=Guarded(torch, "f32", C, ps, off=po),
+             pr=Guarded(torch, "f32", C, ps, off=po), grp=Guarded(torch, "i32", C, gs, off=go, cell=4),
+             clip=Guarded(torch, "f32", 1, C))
+    for k in ("cnt", "st", "pil", "ind", "gcnt"):
+        G[k] = Guarded(torch, "i32", 1, C)
+    out = fmx.BlockOut(G["mpx"].ptr, ms, G["pl"].ptr, G["pr"].ptr, ps, G["cnt"].ptr, G["st"].ptr, G["pil"].ptr,
+                       G["clip"].ptr, G["grp"].ptr, gs, G["gcnt"].ptr, None, G["ind"].ptr)
+    if ktimes is not None:
+        h.timing_enable(True)
+    res = []
+    for b in range(nblk):
+        for g in G.values():
+            g.fill()
+        torch.cuda.synchronize()
+        h.process_block(iq_base + b * 2 * n * M, iq_stride, n, out)
+        h.sync()
+        R = {k: g.raw() for k, g in G.items()}
+        vec = {k: G[k].view(R[k], np.float32 if k == "clip" else np.int32)[0].copy()
+               for k in ("cnt", "st", "pil", "ind", "gcnt", "clip")}
+        tag = ("block", b)
+        for k in vec:
+            G[k].check(C, tag + (k,), R[k])
+        assert np.all(vec["cnt"] >= 0) and np.all(vec["cnt"] <= ps), (tag, vec["cnt"])
+        assert np.all(vec["gcnt"] >= 0), (tag, vec["gcnt"])
+        G["mpx"].check(n, tag + ("mpx",), R["mpx"])
+        G["pl"].check(vec["cnt"], tag + ("pcm_l",), R["pl"])
+        G["pr"].check(vec["cnt"], tag + ("pcm_r",), R["pr"])
+        G["grp"].check(np.minimum(vec["gcnt"], gs), tag + ("groups",), R["grp"])
+        rec = G["grp"].view(R["grp"]).view(np.uint8)
+        res.append(dict(mpx=G["mpx"].view(R["mpx"], np.float32)[:, :n].copy(),
+                        pcm_l=G["pl"].view(R["pl"], np.float32).copy(), pcm_r=G["pr"].view(R["pr"], np.float32).copy(),
+                        count=vec["cnt"], stereo=vec["st"], pilot=vec["pil"], clip=vec["clip"], indicator=vec["ind"],
+                        groups=records_to_groups(rec, vec["gcnt"], gs), gcount=vec["gcnt"]))
+    if ktimes is not None:
+        ktimes.update(h.kernel_times())
+    h.close()
+    del keep
+    return res
+
+
+def run_gpu_unsynchronised(fmx, torch, cfg, d_iq, row, C, nblk, shared_mpx):
+    """The bench's calling pattern -- every block through fmx_process_block
+    with NO host synchronisation in between -- with either one MPX buffer that
+    every call is given (shared_mpx) or one per block.  Every other output
+    goes to per-block buffers.  -> dict of host arrays [nblk][C]...; "mpx":
+    the last block's."""
+    B = cfg.block
+    M = cfg.iq_rate // cfg.dsp_rate
+    dev = torch.device("cuda")
+    h = fmx.Handle(cfg, C)
+    GS = 8
+    f = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)  # noqa: E731
+    z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)  # noqa: E731
+    T = dict(pl=f(nblk, C, B), pr=f(nblk, C, B), clip=f(nblk, C), cnt=z(nblk, C), st=z(nblk, C), pil=z(nblk, C),
+             ind=z(nblk, C), gcnt=z(nblk, C), grp=z(nblk, C, GS, 4))
+    mpx = f(1 if shared_mpx else nblk, C, B)
+    torch.cuda.synchronize()
+    for b in range(nblk):
+        m = mpx[0 if shared_mpx else b]
+        out = fmx.BlockOut(m.data_ptr(), B, T["pl"][b].data_ptr(), T["pr"][b].data_ptr(), B, T["cnt"][b].data_ptr(),
+                           T["st"][b].data_ptr(), T["pil"][b].data_ptr(), T["clip"][b].data_ptr(),
+                           T["grp"][b].data_ptr(), GS, T["gcnt"][b].data_ptr(), None, T["ind"][b].data_ptr())
+        h.process_block(d_iq.data_ptr() + b * 2 * B * M, row, B, out)
+    h.sync()
+    torch.cuda.synchronize()
+    res = {k: v.cpu().numpy() for k, v in T.items()}
+    res["mpx"] = mpx[-1].cpu().numpy()
+    h.close()
+    return res
+
+
+# ---- the stage entry points over 19 channels: call schedule and oracle objects ----
+# (tests/test_gpu_abi_geometry.py runs it on the GPU, tests/test_abi_stage_plan.py
+# checks on the CPU that the oracle decides this input the same way under ten
+# times the GPU's MPX error)
+STAGE_C = 19
+STAGE_CH0 = 700
+# call sizes: whole blocks, then ragged ones (1, 2 and 17 samples, sizes that
+# are no multiple of 16 or of 4, 1023 / 1024 / 1025 around k_fe8's least call),
+# then whole blocks until RDS groups appear
+STAGE_SIZES = [4096, 4096, 333, 1, 17, 1500, 4096, 2, 1023, 1024, 1025, 4096, 4096, 4096] + [4096] * 8
+STAGE_RESETS = {6: (5, 18)}  # before call 6: fmx_reset of channels 5 and 18
+# before call 8, (key, value, channel) of fmx_set_param
+STAGE_PARAMS = {8: (("force_mono", 1, 2), ("deemph_us", 60, 16), ("deviation_hz", 70000, 1))}
+
+
+def stage_iq(fmx, iq_rate=2_400_000, M=10, C=STAGE_C, ch0=STAGE_CH0, sizes=STAGE_SIZES, kind=2, **synth):
+    """uint8 [C][2 * sum(sizes) * M] of the synthetic plan's channels ch0 .. ch0 + C - 1."""
+    scfg = fmx.make_synth(iq_rate=iq_rate, kind=kind, n_bits=8192, **synth)
+    bits, _ = fmx.synth_rds_bits(scfg, ch0, C)
+    return fmx.synth_host(scfg, ch0, C, 0, sum(sizes) * M, bits)
+
+
+class OracleChannel:
+    """One channel's five reference objects as constructed (75 us, the ctor's
+    IQ filter), with the resets and setters of the stage schedule."""
+
+    def __init__(self, oracle, M=10, fs=240_000):
+        self.o, self.L = oracle, oracle.lib()
+        L = self.L
+        tpp = 28 if M >= 8 else (20 if M >= 4 else 12)
+        self.dec = L.oracle_decim_create(M, tpp, 80.0) if M > 1 else None
+        self.dem = L.oracle_demod_create(fs, 32_000)
+        self.ste = L.oracle_stereo_create(fs, 32_000)
+        self.af = L.oracle_afpost_create(fs, 32_000)
+        self.rds = L.oracle_rds_create(fs)
+        self.M = M
+
+    def close(self):
+        L = self.L
+        if self.dem is None:
+            return
+        if self.dec:
+            L.oracle_decim_destroy(self.dec)
+        L.oracle_demod_destroy(self.dem)
+        L.oracle_stereo_destroy(self.ste)
+        L.oracle_afpost_destroy(self.af)
+        L.oracle_rds_destroy(self.rds)
+        self.dem = None
+
+    __del__ = close
+
+    def reset(self):
+        L = self.L
+        if self.dec:
+            L.oracle_decim_reset(self.dec)
+        L.oracle_demod_reset(self.dem)
+        L.oracle_stereo_reset(self.ste)
+        L.oracle_afpost_reset(self.af)
+        L.oracle_rds_reset(self.rds)
+
+    def set_param(self, key, value):
+        L = self.L
+        if key == "force_mono":
+            L.oracle_stereo_set(self.ste, 2, value)
+        elif key == "deemph_us":
+            L.oracle_demod_set(self.dem, 1, value)
+            L.oracle_afpost_set_deemphasis(self.af, value)
+        elif key == "deviation_hz":
+            L.oracle_demod_set(self.dem, 5, value)
+        else:
+            raise KeyError(key)
+
+    def decimate(self, iq_u8, n):
+        out = np.zeros(2 * max(n, 1), np.float32)
+        x = np.ascontiguousarray(iq_u8)
+        k = self.L.oracle_decim_execute_complex(self.dec, x.ctypes.data, n * self.M, out.ctypes.data, n)
+        assert k == n, (k, n)
+        return out[:2 * n]
+
+    def decimate_u8(self, iq_u8, n):
+        out = np.zeros(2 * max(n, 1), np.uint8)
+        x = np.ascontiguousarray(iq_u8)
+        k = self.L.oracle_decim_execute(self.dec, x.ctypes.data, n * self.M, out.ctypes.data, n)
+        assert k == n, (k, n)
+        return out[:2 * n]
+
+    def demod(self, bb, n):
+        """-> (mpx [n], mono [k])"""
+        x = np.ascontiguousarray(bb, dtype=np.float32)
+        mpx, mono = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        k = self.L.oracle_demod_process_split_complex(self.dem, x.ctypes.data, mpx.ctypes.data, mono.ctypes.data, n)
+        return mpx[:n], mono[:k]
+
+    def demod_u8(self, iq_u8, n):
+        """-> (mpx [n], mono [k], clip ratio)"""
+        x = np.ascontiguousarray(iq_u8)
+        mpx, mono = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        k = self.L.oracle_demod_process_split(self.dem, x.ctypes.data, mpx.ctypes.data, mono.ctypes.data, n)
+        return mpx[:n], mono[:k], float(self.L.oracle_demod_clip_ratio(self.dem))
+
+    def downsample(self, mpx, n):
+        x = np.ascontiguousarray(mpx, dtype=np.float32)
+        out = np.zeros(max(n, 1), np.float32)
+        k = self.L.oracle_demod_downsample(self.dem, x.ctypes.data, out.ctypes.data, n)
+        return out[:k]
+
+    def stereo(self, mpx, n):
+        """-> (left [n], right [n], stereo flag, pilot tenths)"""
+        import ctypes as Ct
+        x = np.ascontiguousarray(mpx, dtype=np.float32)
+        l, r = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        s, p = Ct.c_int(), Ct.c_int()
+        k = self.L.oracle_stereo_process(self.ste, x.ctypes.data, l.ctypes.data, r.ctypes.data, n, Ct.byref(s),
+                                         Ct.byref(p))
+        assert k == n, (k, n)
+        return l[:n], r[:n], s.value, p.value
+
+    def afpost(self, left, right, n, cap):
+        x, y = np.ascontiguousarray(left, dtype=np.float32), np.ascontiguousarray(right, dtype=np.float32)
+        ol, orr = np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.float32)
+        k = self.L.oracle_afpost_process(self.af, x.ctypes.data, y.ctypes.data, n, ol.ctypes.data, orr.ctypes.data,
+                                         cap)
+        return ol[:k], orr[:k]
+
+    def rds_groups(self, mpx, n):
+        x = np.ascontiguousarray(mpx, dtype=np.float32)
+        g = (self.o.OracleGroup * 16)()
+        ng = self.L.oracle_rds_process(self.rds, x.ctypes.data, n, g, 16, None, 0, None)
+        assert ng <= 16
+        return self.o.groups_to_tuples(g, ng)
+
+
+def stage_events(ch, i, c):
+    """Apply call i's resets and setters of the stage schedule to OracleChannel
+    ch of channel c."""
+    if c in STAGE_RESETS.get(i, ()):
+        ch.reset()
+    for (key, value, cc) in STAGE_PARAMS.get(i, ()):
+        if cc == c:
+            ch.set_param(key, value)

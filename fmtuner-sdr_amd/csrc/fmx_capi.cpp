@@ -98,10 +98,8 @@ struct Handle {
   // one lane per channel, a few SIMDs) and step k-1's audio still run; the
   // audio of step k overlaps the PLL of step k+1 (raw L/R double-buffered).
   hipStream_t sA = nullptr, sB = nullptr, sC = nullptr, sD = nullptr;
-  hipStream_t sP = nullptr; // k_pilot's stream: sA, or its own (FMX_PILOT_STREAM A/B)
   hipEvent_t evA[FMX_NBUF] = {}, evB[FMX_NBUF] = {}, evC[FMX_NBUF] = {}, evD[FMX_NBUF] = {};
   hipEvent_t evP[FMX_NBUF] = {}; // k_pilot (sA, after k_fe8): k_pll's input
-  hipEvent_t evR[FMX_NBUF] = {}; // k_rs on sA (FMX_RS_ON_A_MAXC): k_rds's input
   hipEvent_t evF[FMX_FRING] = {}; // process_block's front end of step k: evF[k % FMX_FRING]
   // host waits on pinned-image reuse (fmx_host_stats): waits, waits that
   // found the event pending (the host blocked), milliseconds blocked
@@ -152,8 +150,8 @@ struct Handle {
   // row stride (floats) of the MPX / pilot / raw L/R intermediates: the block
   // rounded up to 32 and, when that is a multiple of 256 (1 KB), one 128-B
   // line more (round 6), so that the rows a workgroup reads side by side do
-  // not all fall into the same L2 sets (a build with -DFMX_ROW_PAD=0: the
-  // block itself; 2048 channels 0.3481 -> 0.3412 ms, profiles/r06o_*)
+  // not all fall into the same L2 sets (against rows of the block itself:
+  // 2048 channels 0.3481 -> 0.3412 ms, profiles/r06o_*)
   int row = 0;
   // the intermediate slot the last k_rds read (its RDS-rate input stays there
   // until the next RDS call): the ring refill's source (FmxRdsState::ring_ok)
@@ -740,7 +738,6 @@ static void destroy(Handle *h) {
   if (h->sB) hipStreamSynchronize(h->sB);
   if (h->sC) hipStreamSynchronize(h->sC);
   if (h->sD) hipStreamSynchronize(h->sD);
-  if (h->sP) hipStreamSynchronize(h->sP);
   for (auto &p : h->pending) {
     hipEventDestroy(p.a);
     if (p.b_pool) hipEventDestroy(p.b);
@@ -753,7 +750,7 @@ static void destroy(Handle *h) {
   }
   for (void *p : h->allocs) hipFree(p);
   for (int b = 0; b < FMX_NBUF; ++b)
-    for (hipEvent_t e : {h->evA[b], h->evB[b], h->evC[b], h->evD[b], h->evP[b], h->evR[b]})
+    for (hipEvent_t e : {h->evA[b], h->evB[b], h->evC[b], h->evD[b], h->evP[b]})
       if (e) hipEventDestroy(e);
   for (hipEvent_t e : h->evF)
     if (e) hipEventDestroy(e);
@@ -761,7 +758,6 @@ static void destroy(Handle *h) {
   if (h->evTmpC) hipEventDestroy(h->evTmpC);
   if (h->evTmpD) hipEventDestroy(h->evTmpD);
   if (h->evTmpU) hipEventDestroy(h->evTmpU);
-  if (h->sP && h->sP != h->sA) hipStreamDestroy(h->sP);
   if (h->sD && h->sD != h->sA) hipStreamDestroy(h->sD);
   if (h->sC && h->sC != h->sA) hipStreamDestroy(h->sC);
   if (h->sB && h->sB != h->sA) hipStreamDestroy(h->sB);
@@ -832,23 +828,17 @@ static int create(const fmx_config *cfg, int n, int device, Handle **out) {
     HIP_TRY(hipStreamCreateWithPriority(&h->sA, hipStreamNonBlocking, hi));
   }
 #endif
-#ifndef FMX_PILOT_STREAM
-#define FMX_PILOT_STREAM 0 // A/B: k_pilot on a fifth stream (after the front end's event) instead of sA
-#endif
   if (serial) {
-    h->sB = h->sC = h->sD = h->sP = h->sA;
+    h->sB = h->sC = h->sD = h->sA;
   } else {
     HIP_TRY(hipStreamCreateWithFlags(&h->sB, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&h->sC, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&h->sD, hipStreamNonBlocking));
-    h->sP = h->sA;
-    if (FMX_PILOT_STREAM) HIP_TRY(hipStreamCreateWithFlags(&h->sP, hipStreamNonBlocking));
   }
   for (int b = 0; b < FMX_NBUF; ++b) {
     HIP_TRY(hipEventCreateWithFlags(&h->evA[b], ev_flags(true)));
     HIP_TRY(hipEventCreateWithFlags(&h->evB[b], ev_flags(true)));
     HIP_TRY(hipEventCreateWithFlags(&h->evP[b], ev_flags(true)));
-    HIP_TRY(hipEventCreateWithFlags(&h->evR[b], ev_flags(true)));
     HIP_TRY(hipEventCreateWithFlags(&h->evC[b], ev_flags(true)));
     HIP_TRY(hipEventCreateWithFlags(&h->evD[b], ev_flags(true)));
   }
@@ -860,14 +850,8 @@ static int create(const fmx_config *cfg, int n, int device, Handle **out) {
   if ((rc = dalloc(h, &h->ddes, 1)) != FMX_OK) return rc;
   HIP_TRY(hipMemcpy(h->ddes, h->hdes, sizeof(FmxDesign), hipMemcpyHostToDevice));
   const size_t C = static_cast<size_t>(n);
-#ifndef FMX_ROW_PAD
-#define FMX_ROW_PAD 1
-#endif
-  h->row = cfg->block;
-  if (FMX_ROW_PAD) {
-    h->row = (cfg->block + 31) & ~31;
-    if (h->row % 256 == 0) h->row += 32;
-  }
+  h->row = (cfg->block + 31) & ~31;
+  if (h->row % 256 == 0) h->row += 32;
   const size_t B = static_cast<size_t>(h->row);
   // parameters: the reference objects as main.cpp:640-710 configures them
   h->hpar.assign(C, FmxChanParam{});
@@ -1099,20 +1083,30 @@ static void step_done(Handle *h, bool stereo_hist_written) {
 // k_rs on sD ahead of k_audio, with k_audio no longer waiting for k_rds --
 // 0.427 -> 0.437 ms per step at 2 048 channels, 0.744 -> 0.753 at 4 096,
 // profiles/r04k_ab_rs_stream.txt.)
-static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n, const fmx_block_out *o) {
+// Each stream's part of a step is one function below, in that order, which is
+// also the order process_block calls them in.
+
+// the values of one process_block step that its four streams share
+struct Step {
+  const uint8_t *d_iq;
+  size_t iq_stride;
+  int n;
+  const fmx_block_out *o; // the outputs
+  bool stereo, rds;
+  int buf;                // the intermediates' slot, step mod FMX_NBUF
+  float *mpx;             // the caller's MPX rows, or slot buf's
+  int mpx_stride;
+  hipEvent_t evFE;        // the front end's completion, evF[step % FMX_FRING]
+  // set by step_sA:
+  bool use_rs = false;          // the RDS resampler runs as k_rs (else inside the front end)
+  bool pil_k = false;           // the pilot BPF runs as k_pilot (else inside the front end)
+  bool rds_reset_on_a = false;  // the RDS reset part ran on sA, ahead of the front end
+};
+
+// sA: [wait evD(k-3)] [RDS schedule copy] front end -> evF(k), k_pilot -> evP(k)
+static int step_sA(Handle *h, Step &s) {
   int rc;
-  if ((rc = check_n(h, n)) != FMX_OK) return rc;
-  if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count || !d_iq) {
-    h->err = "process_block: d_iq, d_pcm_l, d_pcm_r and d_pcm_count are required";
-    return FMX_E_INVALID;
-  }
-  if (n == 0) return FMX_OK;
-  if ((rc = prepare_pipelined(h)) != FMX_OK) return rc;
-  if (h->timing) harvest_timing(h);
-  const bool stereo = h->cfg.stereo != 0;
-  const bool rds = h->cfg.rds != 0;
-  const int buf = static_cast<int>(h->step % FMX_NBUF);
-  const int prev = (buf + FMX_NBUF - 1) % FMX_NBUF;
+  const int prev = (s.buf + FMX_NBUF - 1) % FMX_NBUF;
   // slot buf was last read by step k-FMX_NBUF; a caller-owned MPX buffer by
   // step k-1's readers
 #if FMX_DIAG
@@ -1124,38 +1118,34 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
   // each costs the front end ~5 us at its launch even when its event
   // completed long before.  With the bench's timing on,
   // step k-3's audio has finished by the time step k is submitted.
-  auto wait_pending = [](hipStream_t s, hipEvent_t e) {
-    return hipEventQuery(e) == hipSuccess ? hipSuccess : hipStreamWaitEvent(s, e, 0);
+  auto wait_pending = [](hipStream_t stream, hipEvent_t e) {
+    return hipEventQuery(e) == hipSuccess ? hipSuccess : hipStreamWaitEvent(stream, e, 0);
   };
   if (!wait_a) {
-  } else if (o->d_mpx && h->evD_set[prev]) HIP_TRY(wait_pending(h->sA, h->evD[prev]));
-  else if (h->evD_set[buf]) HIP_TRY(wait_pending(h->sA, h->evD[buf]));
+  } else if (s.o->d_mpx && h->evD_set[prev]) HIP_TRY(wait_pending(h->sA, h->evD[prev]));
+  else if (h->evD_set[s.buf]) HIP_TRY(wait_pending(h->sA, h->evD[s.buf]));
   // RDS resampler schedule of this step (read by k_rs, or by the front end):
   // the slot the previous front end filled when the speculation holds, else a
   // copy kernel on sA; then the next step's, copied by this front end into
   // slot k+1 of FMX_SSLOTS, last read by step k-3's k_rs (sC) -- before
   // evD(k-3), which the front end waits for: no second wait
   const int rslot = static_cast<int>(h->step % FMX_SSLOTS), nrslot = static_cast<int>((h->step + 1) % FMX_SSLOTS);
-  if (rds && (rc = tset_take_or_advance(h, h->t_rds, n, rslot, h->sA)) != FMX_OK) return rc;
-  const unsigned spec16 = rds ? tset_speculate(h, h->t_rds, n, nrslot, static_cast<size_t>(h->C) * 256) : 0u;
-  float *mpx = o->d_mpx ? o->d_mpx : h->mpx[buf];
-  const int mpx_stride = o->d_mpx ? o->mpx_stride : h->row;
-  hipEvent_t evFE = h->evF[h->step % FMX_FRING];
-  bool use_rs = false, pil_k = false, rds_reset_on_a = false;
+  if (s.rds && (rc = tset_take_or_advance(h, h->t_rds, s.n, rslot, h->sA)) != FMX_OK) return rc;
+  const unsigned spec16 = s.rds ? tset_speculate(h, h->t_rds, s.n, nrslot, static_cast<size_t>(h->C) * 256) : 0u;
   // ---- front end (sA) ----
   {
-    FeArgs a = fe_args(h, n, h->M > 1 ? FE_IN_U8_DECIM : FE_IN_U8_DIRECT, buf);
-    a.iq = d_iq;
-    a.iq_stride = iq_stride;
-    a.mpx_out = mpx;
-    a.mpx_stride = mpx_stride;
+    FeArgs a = fe_args(h, s.n, h->M > 1 ? FE_IN_U8_DECIM : FE_IN_U8_DIRECT, s.buf);
+    a.iq = s.d_iq;
+    a.iq_stride = s.iq_stride;
+    a.mpx_out = s.mpx;
+    a.mpx_stride = s.mpx_stride;
     a.do_demod = 1;
-    if (stereo) {
-      a.pilot_out = h->pilot[buf];
+    if (s.stereo) {
+      a.pilot_out = h->pilot[s.buf];
       a.pilot_stride = h->row;
     }
-    if (rds) {
-      a.rds_out = h->rds_in[buf];
+    if (s.rds) {
+      a.rds_out = h->rds_in[s.buf];
       a.rds_stride = h->rds_stride;
     }
     // the RDS resampler of a k_fe8 step runs as k_rs (MFMA tiles of 16
@@ -1168,22 +1158,18 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
     // 16-B loads: only on a 16-B aligned base with a stride of whole 16-B
     // groups.  Any other caller geometry keeps the resampler inside k_fe8
     // (its RS = true instance, scalar MPX stores): correct, slower.
-    const bool mpx_vec16 = ((reinterpret_cast<uintptr_t>(mpx) | (static_cast<uintptr_t>(mpx_stride) * 4)) & 15) == 0;
-    use_rs = rds && h->hdes->rds_del <= 2.1f && h->t_rds.G == 1 && fe8 && mpx_vec16;
+    const bool mpx_vec16 = ((reinterpret_cast<uintptr_t>(s.mpx) | (static_cast<uintptr_t>(s.mpx_stride) * 4)) & 15) == 0;
+    s.use_rs = s.rds && h->hdes->rds_del <= 2.1f && h->t_rds.G == 1 && fe8 && mpx_vec16;
     // the pilot BPF of a k_fe8 step runs as k_pilot (after it, on sA): k_fe8
     // writes the MPX and the stereo history rows k_pilot starts from
-    // (FMX_FE_PILOT, A/B: inside k_fe8's RS = true instance, no k_pilot)
-#ifndef FMX_FE_PILOT
-#define FMX_FE_PILOT 0
-#endif
-    pil_k = stereo && fe8 && !FMX_FE_PILOT;
-    if (pil_k) {
+    s.pil_k = s.stereo && fe8;
+    if (s.pil_k) {
       a.pilot_out = nullptr;
       a.st_hist_out = 1;
     }
-    if (use_rs) a.rds_win_out = h->rds_win[buf];
-    a.clip_out = o->d_clip_ratio ? o->d_clip_ratio : h->clip;
-    a.sig_sums = o->d_signal ? h->sig_sums[buf] : nullptr;
+    if (s.use_rs) a.rds_win_out = h->rds_win[s.buf];
+    a.clip_out = s.o->d_clip_ratio ? s.o->d_clip_ratio : h->clip;
+    a.sig_sums = s.o->d_signal ? h->sig_sums[s.buf] : nullptr;
     if (spec16) {
       a.next_sched_src = h->t_rds.h_dev[h->t_rds.spec_img];
       a.next_sched_dst = h->t_rds.d_slot[nrslot];
@@ -1196,85 +1182,68 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
     // front end and behind the RDS stream's earlier work, instead of on sC
     // behind the front end.  (With k_rs the row is written on sC, after the
     // reset part.)
-    if (rds && !use_rs && h->rds_last_buf == buf && !h->rl_pending.empty()) {
+    if (s.rds && !s.use_rs && h->rds_last_buf == s.buf && !h->rl_pending.empty()) {
       HIP_TRY(hipEventRecord(h->evTmpC, h->sC));
       HIP_TRY(hipStreamWaitEvent(h->sA, h->evTmpC, 0));
       if ((rc = launch_reset_parts(h, RSP_RDS, h->sA)) != FMX_OK) return rc;
-      rds_reset_on_a = true;
+      s.rds_reset_on_a = true;
     }
-    KBind t(h, fe8 ? FMX_K_FRONTEND : FMX_K_FRONTEND_GENERIC, h->sA, evFE);
+    KBind t(h, fe8 ? FMX_K_FRONTEND : FMX_K_FRONTEND_GENERIC, h->sA, s.evFE);
     if ((rc = launch_frontend_m(a, h->M, h->hdes->dec_tpp, h->sA, dec_warm(h))) != FMX_OK) {
       h->err = "frontend launch failed";
       h->t_rds.spec = false; // the next step's schedule was not copied
       return rc;
     }
     t.launched();
-    dec_advance(h, n);
+    dec_advance(h, s.n);
   }
   if (spec16) { // the pinned image is reused FMX_HSLOTS simulations later: its read ends with the front end
-    h->t_rds.ev_use[h->t_rds.spec_img] = evFE;
+    h->t_rds.ev_use[h->t_rds.spec_img] = s.evFE;
     h->t_rds.ev_h_set[h->t_rds.spec_img] = true;
   }
-  // ---- pilot BPF (after the front end; read by k_pll): on sA, or with
-  // FMX_PILOT_ON_B on sB ahead of k_pll ----
-#ifndef FMX_PILOT_ON_B
-#define FMX_PILOT_ON_B 0
-#endif
-  hipStream_t sPil = FMX_PILOT_ON_B ? h->sB : h->sP;
-  if (pil_k && (FMX_PILOT_ON_B || sPil != h->sA)) HIP_TRY(hipStreamWaitEvent(sPil, evFE, 0));
-  // FMX_PILOT_SPLIT_PCT (A/B): that share of the channels (rounded down to 8)
-  // has its pilot BPF on sB, ahead of k_pll, the rest stays on sA
-#ifndef FMX_PILOT_SPLIT_PCT
-#define FMX_PILOT_SPLIT_PCT 0
-#endif
-  const int pil_cB = (pil_k && !FMX_PILOT_ON_B && sPil == h->sA && h->sB != h->sA)
-                         ? ((h->C * FMX_PILOT_SPLIT_PCT / 100) & ~7) : 0;
-  auto run_pilot = [&](int c0, int cn, hipStream_t s, hipEvent_t done) -> int {
+  // ---- pilot BPF (sA, after the front end; read by k_pll) ----
+  if (s.pil_k) {
     PilotArgs p{};
     p.des = h->ddes;
     p.des_pilot_len = h->hdes->pilot_len;
-    p.C = cn;
-    p.n = n;
-    p.mpx = mpx + static_cast<size_t>(c0) * mpx_stride;
-    p.mpx_stride = mpx_stride;
-    p.st_hist_rd = h->st_hist + (static_cast<size_t>(h->st_idx) * h->C + c0) * FMX_HIST;
-    p.out = h->pilot[buf] + static_cast<size_t>(c0) * h->row;
+    p.C = h->C;
+    p.n = s.n;
+    p.mpx = s.mpx;
+    p.mpx_stride = s.mpx_stride;
+    p.st_hist_rd = h->st_hist + static_cast<size_t>(h->st_idx) * h->C * FMX_HIST;
+    p.out = h->pilot[s.buf];
     p.out_stride = h->row;
-    KBind t(h, FMX_K_PILOT, s, done);
+    KBind t(h, FMX_K_PILOT, h->sA, h->evP[s.buf]);
     if (!FMX_SKIP(pll) && !FMX_SKIP(pilot)) {
-      if (launch_pilot(p, s) != FMX_OK) {
+      if (launch_pilot(p, h->sA) != FMX_OK) {
         h->err = "pilot launch failed";
         return FMX_E_HIP;
       }
       t.launched();
     }
-    return FMX_OK;
-  };
-  if (pil_k && (rc = run_pilot(0, h->C - pil_cB, sPil, h->evP[buf])) != FMX_OK) return rc;
-  if (pil_cB > 0) {
-    HIP_TRY(hipStreamWaitEvent(h->sB, evFE, 0));
-    if ((rc = run_pilot(h->C - pil_cB, pil_cB, h->sB, nullptr)) != FMX_OK) return rc;
   }
+  return FMX_OK;
+}
+
+// sC: [wait evF(k)] k_rs, k_rds -> evC(k)
+static int step_sC(Handle *h, const Step &s) {
+  int rc;
   // ---- RDS (sC): the 240k -> 171k resampler (k_rs), then k_rds ----
-  // (FMX_RS_ON_A_MAXC: up to that many channels k_rs runs on sA behind
-  // k_pilot instead, so that the RDS stream holds only k_rds -- A/B)
-#ifndef FMX_RS_ON_A_MAXC
-#define FMX_RS_ON_A_MAXC 0
-#endif
-  const bool rs_on_a = rds && use_rs && h->C <= FMX_RS_ON_A_MAXC && h->sA != h->sC;
-  auto run_rs = [&](hipStream_t s, hipEvent_t done) -> int {
+  HIP_TRY(hipStreamWaitEvent(h->sC, s.evFE, 0));
+  if (!s.rds_reset_on_a && (rc = launch_reset_parts(h, RSP_RDS, h->sC)) != FMX_OK) return rc;
+  if (s.use_rs) {
     RsArgs r{};
     r.des = h->ddes;
     r.C = h->C;
-    r.n = n;
-    r.mpx = mpx;
-    r.mpx_stride = mpx_stride;
-    r.win = h->rds_win[buf];
+    r.n = s.n;
+    r.mpx = s.mpx;
+    r.mpx_stride = s.mpx_stride;
+    r.win = h->rds_win[s.buf];
     r.sched = h->t_rds.d_sched[h->t_rds.cur];
     r.sched_n = h->t_rds.d_count[h->t_rds.cur];
     r.group = h->t_rds.d_group[h->t_rds.cur];
     r.sched_stride = h->t_rds.stride;
-    r.out = h->rds_in[buf];
+    r.out = h->rds_in[s.buf];
     r.out_stride = h->rds_stride;
     // <= FMX_RS_TMAX output tiles per workgroup (8 parts of 23 tiles at a
     // 4096-sample block); from 256 channel groups (4096 channels) on, <= 46:
@@ -1291,69 +1260,49 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
     const int rs_tiles = (h->t_rds.stride + 15) / 16,
               rs_tmax = rs_groups >= 256 ? 46 : (rs_groups >= 128 ? FMX_RS_TMAX : 6);
     r.parts = std::max(1, (rs_tiles + rs_tmax - 1) / rs_tmax);
-    KBind t(h, FMX_K_RS, s, done);
+    KBind t(h, FMX_K_RS, h->sC, nullptr);
     if (!FMX_SKIP(rds) && !FMX_SKIP(krs)) {
-      if (launch_rs(r, s) != FMX_OK) {
+      if (launch_rs(r, h->sC) != FMX_OK) {
         h->err = "rds resampler launch failed";
         return FMX_E_HIP;
       }
       t.launched();
     }
-    return FMX_OK;
-  };
-  if (rs_on_a && (rc = run_rs(h->sA, h->evR[buf])) != FMX_OK) return rc;
-  // FMX_RS_AFTER_PILOT (A/B): the RDS stream starts behind k_pilot instead of
-  // beside it (k_rs then shares the CUs with the next k_fe8 and k_pll, the
-  // co-residency its 16.5 KB LDS was sized for, not with k_pilot)
-#ifndef FMX_RS_AFTER_PILOT
-#define FMX_RS_AFTER_PILOT 0
-#endif
-  HIP_TRY(hipStreamWaitEvent(h->sC, rs_on_a ? h->evR[buf] : ((FMX_RS_AFTER_PILOT && pil_k) ? h->evP[buf] : evFE), 0));
-  if (!rds_reset_on_a && (rc = launch_reset_parts(h, RSP_RDS, h->sC)) != FMX_OK) return rc;
-  if (rds) {
-    RdsArgs a = rds_args(h, buf);
-    a.groups = o->d_groups;
-    a.groups_stride = o->d_groups ? o->groups_stride : 0;
-    a.group_count = o->d_group_count;
-    // FMX_RDS_FUSED: k_rds produces the 171 kHz samples itself (k_rs's MFMA
-    // tiles inside its rounds): no k_rs launch, no 171 kHz rows in HBM
-    const bool fused = FMX_RDS_FUSED && use_rs && !rs_on_a;
-    if (fused) {
-      a.fused = 1;
-      a.n = n;
-      a.mpx = mpx;
-      a.mpx_stride = mpx_stride;
-      a.win = h->rds_win[buf];
-      a.sched = h->t_rds.d_sched[h->t_rds.cur];
-      a.sched_n = h->t_rds.d_count[h->t_rds.cur];
-      a.group = h->t_rds.d_group[h->t_rds.cur];
-      a.sched_stride = h->t_rds.stride;
-    } else if (use_rs && !rs_on_a && (rc = run_rs(h->sC, nullptr)) != FMX_OK) {
-      return rc;
-    }
-    KBind t(h, FMX_K_RDS, h->sC, h->evC[buf]);
+  }
+  if (s.rds) {
+    RdsArgs a = rds_args(h, s.buf);
+    a.groups = s.o->d_groups;
+    a.groups_stride = s.o->d_groups ? s.o->groups_stride : 0;
+    a.group_count = s.o->d_group_count;
+    KBind t(h, FMX_K_RDS, h->sC, h->evC[s.buf]);
     if (!FMX_SKIP(rds)) {
       if ((rc = launch_rds_sym(a, h->sC)) != FMX_OK) {
         h->err = "rds launch failed";
         return rc;
       }
       t.launched();
-      if (!a.fused) h->rds_last_buf = buf;
+      h->rds_last_buf = s.buf;
     }
   } else {
-    if (o->d_group_count) HIP_TRY(hipMemsetAsync(o->d_group_count, 0, sizeof(int) * h->C, h->sC));
-    HIP_TRY(hipEventRecord(h->evC[buf], h->sC));
+    if (s.o->d_group_count) HIP_TRY(hipMemsetAsync(s.o->d_group_count, 0, sizeof(int) * h->C, h->sC));
+    HIP_TRY(hipEventRecord(h->evC[s.buf], h->sC));
   }
-  h->evC_set[buf] = true;
+  h->evC_set[s.buf] = true;
+  return FMX_OK;
+}
+
+// sB: [wait evP(k)] k_pll -> evB(k)
+static int step_sB(Handle *h, const Step &s) {
+  int rc;
   // ---- stereo PLL (sB) ----
-  if (!(pil_k && FMX_PILOT_ON_B)) HIP_TRY(hipStreamWaitEvent(h->sB, pil_k ? h->evP[buf] : evFE, 0));
+  HIP_TRY(hipStreamWaitEvent(h->sB, s.pil_k ? h->evP[s.buf] : s.evFE, 0));
   if ((rc = launch_reset_parts(h, RSP_STEREO, h->sB)) != FMX_OK) return rc;
-  if (stereo) {
-    PllArgs a = pll_args(h, n, mpx, mpx_stride, buf);
-    a.stereo_out = o->d_stereo;
-    a.pilot_tenths_out = o->d_pilot_tenths;
-    a.indicator_out = o->d_stereo_indicator;
-    KBind t(h, FMX_K_STEREO, h->sB, h->evB[buf]);
+  if (s.stereo) {
+    PllArgs a = pll_args(h, s.n, s.mpx, s.mpx_stride, s.buf);
+    a.stereo_out = s.o->d_stereo;
+    a.pilot_tenths_out = s.o->d_pilot_tenths;
+    a.indicator_out = s.o->d_stereo_indicator;
+    KBind t(h, FMX_K_STEREO, h->sB, h->evB[s.buf]);
     if (!FMX_SKIP(pll)) {
       if ((rc = launch_pll(a, h->sB)) != FMX_OK) {
         h->err = "pll launch failed";
@@ -1362,12 +1311,18 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
       t.launched();
     }
   } else {
-    if (o->d_stereo) HIP_TRY(hipMemsetAsync(o->d_stereo, 0, sizeof(int) * h->C, h->sB));
-    if (o->d_pilot_tenths) HIP_TRY(hipMemsetAsync(o->d_pilot_tenths, 0, sizeof(int) * h->C, h->sB));
-    if (o->d_stereo_indicator) HIP_TRY(hipMemsetAsync(o->d_stereo_indicator, 0, sizeof(int) * h->C, h->sB));
-    HIP_TRY(hipEventRecord(h->evB[buf], h->sB));
+    if (s.o->d_stereo) HIP_TRY(hipMemsetAsync(s.o->d_stereo, 0, sizeof(int) * h->C, h->sB));
+    if (s.o->d_pilot_tenths) HIP_TRY(hipMemsetAsync(s.o->d_pilot_tenths, 0, sizeof(int) * h->C, h->sB));
+    if (s.o->d_stereo_indicator) HIP_TRY(hipMemsetAsync(s.o->d_stereo_indicator, 0, sizeof(int) * h->C, h->sB));
+    HIP_TRY(hipEventRecord(h->evB[s.buf], h->sB));
   }
-  h->evB_set[buf] = true;
+  h->evB_set[s.buf] = true;
+  return FMX_OK;
+}
+
+// sD: [wait evC(k)] k_bits, [wait evB(k)] [audio schedule copy] k_audio -> evD(k)
+static int step_sD(Handle *h, const Step &s) {
+  int rc;
   // ---- audio (sD): after the PLL (stereo) / the front end (mono), and
   // after k_rds, so that evD closes the step ----
   // the RDS bit decoders (k_bits) over k_rds's symbols of slot buf, here
@@ -1375,13 +1330,13 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
   // only, k_bits runs beside the next step's k_rs.  It waits for k_rds
   // alone, ahead of the PLL wait, so that it runs beside the tail of k_pll
   // and k_audio starts as soon as k_pll ends
-  HIP_TRY(hipStreamWaitEvent(h->sD, h->evC[buf], 0));
+  HIP_TRY(hipStreamWaitEvent(h->sD, h->evC[s.buf], 0));
   if ((rc = launch_reset_parts(h, RSP_BITS, h->sD)) != FMX_OK) return rc;
-  if (rds && !FMX_SKIP(rds)) {
-    RdsArgs a = rds_args(h, buf);
-    a.groups = o->d_groups;
-    a.groups_stride = o->d_groups ? o->groups_stride : 0;
-    a.group_count = o->d_group_count;
+  if (s.rds && !FMX_SKIP(rds)) {
+    RdsArgs a = rds_args(h, s.buf);
+    a.groups = s.o->d_groups;
+    a.groups_stride = s.o->d_groups ? s.o->groups_stride : 0;
+    a.group_count = s.o->d_group_count;
     KBind t(h, FMX_K_BITS, h->sD, nullptr);
     if ((rc = launch_bits(a, h->sD)) != FMX_OK) {
       h->err = "rds bit decoder launch failed";
@@ -1389,37 +1344,34 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
     }
     t.launched();
   }
-  HIP_TRY(hipStreamWaitEvent(h->sD, h->evB[buf], 0));
+  HIP_TRY(hipStreamWaitEvent(h->sD, h->evB[s.buf], 0));
   if ((rc = launch_reset_parts(h, RSP_AUDIO, h->sD)) != FMX_OK) return rc;
   h->rl_pending.clear();
-  TimingSet *tau = stereo ? &h->t_af : &h->t_mono;
-  if ((rc = tset_advance(h, *tau, n, buf, h->sD, nullptr)) != FMX_OK) return rc;
+  TimingSet *tau = s.stereo ? &h->t_af : &h->t_mono;
+  if ((rc = tset_advance(h, *tau, s.n, s.buf, h->sD, nullptr)) != FMX_OK) return rc;
   {
-    AudioArgs a = audio_args(h, n, stereo ? 0 : 3, tau);
-    if (stereo) {
-      a.in_l = h->lraw[buf];
-      a.in_r = h->rraw[buf];
+    AudioArgs a = audio_args(h, s.n, s.stereo ? 0 : 3, tau);
+    if (s.stereo) {
+      a.in_l = h->lraw[s.buf];
+      a.in_r = h->rraw[s.buf];
       a.in_stride = h->row;
-#ifdef FMX_AB_NO_LR // A/B only: every channel reads the first pair's rows (L2-resident)
-      a.in_stride = 0;
-#endif
       a.in_tiled = lr_tiled(h);
       a.cap = h->cfg.block;
     } else {
-      a.in_l = mpx;
+      a.in_l = s.mpx;
       a.in_r = nullptr;
-      a.in_stride = mpx_stride;
+      a.in_stride = s.mpx_stride;
       a.cap = 1 << 30;
     }
-    a.out_l = o->d_pcm_l;
-    a.out_r = o->d_pcm_r;
-    a.out_stride = o->pcm_stride;
-    a.out_count = o->d_pcm_count;
+    a.out_l = s.o->d_pcm_l;
+    a.out_r = s.o->d_pcm_r;
+    a.out_stride = s.o->pcm_stride;
+    a.out_count = s.o->d_pcm_count;
     a.clamp = 1;
     a.mute = h->mute;
     a.mute_fade = h->cfg.out_rate / 200;
-    audio_signal_level(h, a, o, buf, n);
-    KBind t(h, FMX_K_AUDIO, h->sD, h->evD[buf]);
+    audio_signal_level(h, a, s.o, s.buf, s.n);
+    KBind t(h, FMX_K_AUDIO, h->sD, h->evD[s.buf]);
     if (!FMX_SKIP(audio)) {
       if ((rc = launch_audio(a, h->sD)) != FMX_OK) {
         h->err = "audio launch failed";
@@ -1428,9 +1380,37 @@ static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n
       t.launched();
     }
   }
-  h->evD_set[buf] = true;
+  h->evD_set[s.buf] = true;
+  return FMX_OK;
+}
+
+static int process_block(Handle *h, const uint8_t *d_iq, size_t iq_stride, int n, const fmx_block_out *o) {
+  int rc;
+  if ((rc = check_n(h, n)) != FMX_OK) return rc;
+  if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count || !d_iq) {
+    h->err = "process_block: d_iq, d_pcm_l, d_pcm_r and d_pcm_count are required";
+    return FMX_E_INVALID;
+  }
+  if (n == 0) return FMX_OK;
+  if ((rc = prepare_pipelined(h)) != FMX_OK) return rc;
+  if (h->timing) harvest_timing(h);
+  Step s{};
+  s.d_iq = d_iq;
+  s.iq_stride = iq_stride;
+  s.n = n;
+  s.o = o;
+  s.stereo = h->cfg.stereo != 0;
+  s.rds = h->cfg.rds != 0;
+  s.buf = static_cast<int>(h->step % FMX_NBUF);
+  s.mpx = o->d_mpx ? o->d_mpx : h->mpx[s.buf];
+  s.mpx_stride = o->d_mpx ? o->mpx_stride : h->row;
+  s.evFE = h->evF[h->step % FMX_FRING];
+  if ((rc = step_sA(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sC(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sB(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sD(h, s)) != FMX_OK) return rc;
   h->block_index++;
-  step_done(h, stereo);
+  step_done(h, s.stereo);
   return FMX_OK;
 }
 

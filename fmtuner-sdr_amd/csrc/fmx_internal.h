@@ -53,7 +53,7 @@ struct FeArgs {
   int bb_stride;
   float *mpx_out;
   int mpx_stride;
-  float *pilot_out;  // null = no pilot BPF
+  float *pilot_out;  // null = no pilot BPF (k_frontend only: k_fe8 has none, k_pilot follows it)
   int pilot_stride;
   int st_hist_out;   // write the stereo history rows (st_hist_wr) even without the pilot BPF
   float *rds_out;    // null = no RDS resampling
@@ -165,20 +165,6 @@ struct RdsArgs {
   int sym_stride;
   int *sym_count;     // [C]
   float *sym_last_im; // [C] the last symbol's imaginary part (BiphaseDecoder's prev)
-  // fused (round 6, FMX_RDS_FUSED A/B builds only -- measured slower and not
-  // shipped: +20 % step at 4096 channels, +61 % at 2048, profiles/r06l_*):
-  // k_rds resamples the MPX to 171 kHz itself
-  // (k_rs's MFMA tiles, produced as the rounds need them) instead of reading
-  // `in`; as RsArgs
-  int fused;
-  int n;                  // MPX samples of the call
-  const float *mpx;
-  int mpx_stride;
-  const float *win;       // [C][32] the previous call's last 32 MPX samples
-  const FmxSched *sched;  // [groups][sched_stride]
-  const int *sched_n;     // [groups]
-  const int *group;       // [C]
-  int sched_stride;
 };
 
 // k_pilot: the 19 kHz pilot BPF of a process_block step (after k_fe8)
@@ -231,9 +217,6 @@ struct ResetArgs;
 int launch_rds_sym(const RdsArgs &a, void *stream);  // k_rds alone: the call's symbols
 int launch_ring_fill(const ResetArgs &a, void *stream); // every channel's RDS ring refilled where ring_ok = 0
 int launch_bits(const RdsArgs &a, void *stream);     // k_bits alone: the bit decoders
-#ifndef FMX_RDS_FUSED
-#define FMX_RDS_FUSED 0 // A/B: the RDS resampler inside k_rds (RdsArgs::fused)
-#endif
 #ifndef FMX_RS_TMAX
 #define FMX_RS_TMAX 12 // k_rs: output tiles (of 16) per workgroup at most from 2048 channels (46 from 4096 on, 6 below 2048: fmx_capi.cpp)
 #endif

@@ -1644,9 +1644,8 @@ __device__ __forceinline__ void rds_bits_store(FmxRdsState &g, const RdsBits &b)
   }
   g.bs_bits_since_lost = b.bs_bits_since_lost;
 }
-/* ---- the RDS resampler's MFMA tile (k_rs; round 6: also the producer
- * fused into k_rds, FMX_RDS_FUSED) -- see k_rs below for the band-matrix
- * form ---- */
+/* ---- the RDS resampler's MFMA tile (k_rs) -- see k_rs below for the
+ * band-matrix form ---- */
 #define RS_KS 16   // K steps of 4 per 16-output tile: a 64-sample window (fmx_capi.cpp checks that it holds the tile)
 // the tile's window, sample s of a channel at [c][RS_XS (s mod 4) + s / 4]:
 // a lane's 16 samples of one K column are one 64-B run (4 ds_read_b128
@@ -1797,16 +1796,6 @@ __device__ void rds_ring_fill(const FmxRdsState *sp, const float *prev, float *r
     *reinterpret_cast<f32x2 *>(ring + 2 * idx) = rds_mix(prev[t], w);
   }
 }
-// the fused resampler's LDS (FMX_RDS_FUSED, behind RdsLds): k_rs's tap rows,
-// its window double buffer for the wave's 8 channels, and a ring of the
-// produced 171 kHz samples per channel (output e at [e % RDS_RSR])
-#define RDS_RSR 128
-struct RdsFusedLds {
-  float tab[FMX_NPFB + 1][FMX_RDS_RS_SUB + 1];
-  float xs[2][RDS_CPW][RS_XP] __attribute__((aligned(16)));
-  float rsr[RDS_CPW][RDS_RSR] __attribute__((aligned(16)));
-};
-#define RDS_FOFF ((sizeof(RdsLds) + 15) & ~(size_t)15)
 // k_bits: the bit decoders' LDS (burst-error tables, one bit state per lane)
 struct BitsLds {
   uint32_t esyn[5][52];
@@ -1961,11 +1950,7 @@ __device__ __forceinline__ f32x2 rds_sum8x2(float x, float y) {
 #ifndef FMX_RDS_WPE
 #define FMX_RDS_WPE 3 // k_rds waves per SIMD the register budget allows (A/B switch)
 #endif
-// (FUSED: two waves per SIMD's registers -- the producer's window
-// registers; 512 one-wave workgroups at 4096 channels leave it room beside
-// two k_fe8 waves)
-template <bool FUSED>
-__global__ __launch_bounds__(64, FUSED ? 2 : FMX_RDS_WPE) void k_rds(RdsArgs a) {
+__global__ __launch_bounds__(64, FMX_RDS_WPE) void k_rds(RdsArgs a) {
 #ifndef FMX_RDS_PRIO
 #define FMX_RDS_PRIO 2
 #endif
@@ -2013,7 +1998,7 @@ __global__ __launch_bounds__(64, FUSED ? 2 : FMX_RDS_WPE) void k_rds(RdsArgs a) 
   // checkpoints (FmxRdsState::ck_*); a shorter one writes its samples into
   // the ring, which must then hold the previous call's: refilled here first
   // when that call left checkpoints (the channel's 8 lanes, 32 samples each)
-  const bool ringw = FUSED || a.ring_always || count < FMX_RDS_RING;
+  const bool ringw = a.ring_always || count < FMX_RDS_RING;
   {
     const bool refill = act && count > 0 && count < FMX_RDS_RING && !G.ring_ok && a.in_prev != nullptr;
     if (__ballot(refill)) {
@@ -2115,59 +2100,8 @@ __global__ __launch_bounds__(64, FUSED ? 2 : FMX_RDS_WPE) void k_rds(RdsArgs a) 
                 xin0 + (uint32_t)(((r & (RDS_NR - 1)) * 3 + q) * 64 * 4));
     }
   };
-  // ---- FUSED: the 240k -> 171k resampler inside (k_rs's MFMA tiles for the
-  // wave's 8 channels, columns 8 .. 15 of a tile unused), produced ahead of
-  // the round that reads them: tile T (outputs 16 T .. 16 T + 15 of the
-  // call, the same schedule entries for every channel) when the latest round
-  // position of the wave's channels reaches it.  The window of tile T + 1 is
-  // in registers and that of tile T in LDS when tile T is computed (k_rs's
-  // two-deep pipeline); the schedule entries two tiles ahead. ----
-  RdsFusedLds &F = *reinterpret_cast<RdsFusedLds *>(rds_smem + RDS_FOFF);
-  const FmxSched *fsched = nullptr;
-  int fns = 0, fntile = 0, ft = 0, o0max = 0;
-  FmxSched feC{}, feN{}, feNN{};
-  float4 fwN[4];
-  const int frr = lane & 15, fkk = lane >> 4, flc = lane >> 2, flq = lane & 3;
-  const bool flcv = flc < RDS_CPW && c0 + flc < a.C;
-  const float *fmrow = nullptr, *fwrow = nullptr;
-  auto f_load_e = [&](int T) __attribute__((always_inline)) { return fsched[min(16 * T + frr, fns - 1)]; };
-  if (FUSED) {
-    rs_fill_tab(F.tab, D, lane, 64);
-    const int fg = a.group[c0];
-    fsched = a.sched + (size_t)fg * a.sched_stride;
-    fns = a.sched_n[fg];
-    fntile = (fns + 15) / 16;
-    const int fch = flcv ? c0 + flc : c0;
-    fmrow = a.mpx + (size_t)fch * a.mpx_stride;
-    fwrow = a.win + (size_t)fch * 32 + 32;
-    o0max = o0;
-    for (int d = 32; d >= 1; d >>= 1) o0max = max(o0max, __shfl_xor(o0max, d));
-    feC = f_load_e(0);
-    feN = f_load_e(1);
-    feNN = f_load_e(2);
-    float4 w0[4];
-    rs_load_w(fmrow, fwrow, flcv, a.n, flq, rs_tile_k0(feC), w0);
-    if (flc < RDS_CPW) rs_store_w(F.xs[0][flc], flcv, a.n, flq, rs_tile_k0(feC), w0);
-    rs_load_w(fmrow, fwrow, flcv, a.n, flq, rs_tile_k0(feN), fwN);
-  }
-  auto produce = [&]() __attribute__((always_inline)) {
-    float4 wNN[4];
-    rs_load_w(fmrow, fwrow, flcv, a.n, flq, rs_tile_k0(feNN), wNN); // tile ft + 2
-    const rs_f32x4 acc = rs_tile(F.tab, F.xs[ft & 1][frr & (RDS_CPW - 1)], feC, fkk);
-    if (frr < RDS_CPW)
-      *reinterpret_cast<float4 *>(&F.rsr[frr][(16 * ft + 4 * fkk) & (RDS_RSR - 1)]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    if (flc < RDS_CPW) rs_store_w(F.xs[(ft + 1) & 1][flc], flcv, a.n, flq, rs_tile_k0(feN), fwN); // tile ft + 1
 #pragma unroll
-    for (int j = 0; j < 4; ++j) fwN[j] = wNN[j];
-    feC = feN;
-    feN = feNN;
-    feNN = f_load_e(ft + 3);
-    ++ft;
-  };
-  if (!FUSED) {
-#pragma unroll
-    for (int p = 0; p < RDS_PF; ++p) dma_round(p);
-  }
+  for (int p = 0; p < RDS_PF; ++p) dma_round(p);
   __syncthreads(); // LDS tables and per-channel state written
   int ckp = 0; // checkpoint slot of round r: r % FMX_RDS_CK
   // the lane's tap columns: the first FMX_RDS_HREG held in registers for
@@ -2183,25 +2117,13 @@ __global__ __launch_bounds__(64, FUSED ? 2 : FMX_RDS_WPE) void k_rds(RdsArgs a) 
   RDS_STAMP(0)
   for (int r = 0; r < rmax; ++r) {
     float xr0[3];
-    if (FUSED) {
-      // the wave's latest sample this round: o0 + 24 r of its latest channel
-      const int eneed = min((r == 0) ? o0max : o0max + FMX_RDS_DECIM * r, fns - 1);
-      while (ft < fntile && 16 * ft <= eneed) produce();
-      const int fbase = (r == 0) ? o0 - (FMX_RDS_DECIM - 1) : o0 + 1 + FMX_RDS_DECIM * (r - 1);
+    dma_round(r + RDS_PF);
+    // the moves of rounds r + 1 .. r + RDS_PF may stay in flight (anything
+    // the compiler issued after them only makes the wait stricter)
+    // vmcnt(3 RDS_PF) (its bits 3:0 and 15:14), lgkmcnt / expcnt untouched
+    __builtin_amdgcn_s_waitcnt(0x0F70 | ((3 * RDS_PF) & 15) | (((3 * RDS_PF) >> 4) << 14));
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int t = fbase + 3 * j0 + q;
-        xr0[q] = F.rsr[g][t & (RDS_RSR - 1)]; // t outside [0, count) is masked below (vq)
-      }
-    } else {
-      dma_round(r + RDS_PF);
-      // the moves of rounds r + 1 .. r + RDS_PF may stay in flight (anything
-      // the compiler issued after them only makes the wait stricter)
-      // vmcnt(3 RDS_PF) (its bits 3:0 and 15:14), lgkmcnt / expcnt untouched
-      __builtin_amdgcn_s_waitcnt(0x0F70 | ((3 * RDS_PF) & 15) | (((3 * RDS_PF) >> 4) << 14));
-#pragma unroll
-      for (int q = 0; q < 3; ++q) xr0[q] = L.xin[r & (RDS_NR - 1)][q][lane];
-    }
+    for (int q = 0; q < 3; ++q) xr0[q] = L.xin[r & (RDS_NR - 1)][q][lane];
     // this lane's tap columns for the FIR products below: all eleven reads
     // issued here, ahead of the mix-down, which hides their latency (round 4
     // interleaved one read per accumulator with its packed FMAs: eleven LDS
@@ -2697,7 +2619,6 @@ __global__ void k_synth(fmx_synth_config cfg, uint32_t ch0, int n_ch, int64_t sa
  *                 FMAs; the window is fully unrolled, zero taps never issued
  *   DC blockers   8-element affine maps per thread, block scan, recompute
  *   IQ FIR        complex: 1 ds_read_b64 per input -> 8 packed FMAs
- *   pilot BPF     1 ds_read_b32 per input -> 4 packed FMAs (output pairs)
  *   RDS resampler packed (branch, next branch) chain on the MPX image
  * The IQ and MPX images in LDS are padded (element i at i + i/8): lanes 8
  * elements apart read distinct banks.  The complex IQ image and the IQ FIR
@@ -2740,24 +2661,17 @@ template <int M, int TPP, bool RS = true> struct Fe8Layout {
   static constexpr int R0 = ((RAW_ALLOC > YB + YB_BYTES ? RAW_ALLOC : YB + YB_BYTES) + 15) & ~15;
   // unpadded MPX copy for the RDS resampler (32 history + chunk + 32 slack),
   // at the top of the raw region: the pieces below it are the next chunk's
-  // early DMA (during pilot / RDS), the pieces over it the late DMA
+  // early DMA (during the RDS resampler), the pieces over it the late DMA
   static constexpr int U_FLOATS = 32 + FE8_T + 32;
   static constexpr int UOFF = (R0 - U_FLOATS * 4) & ~15;
   static constexpr int NPC_EARLY = UOFF / 1024 < NPC ? UOFF / 1024 : NPC;
   static constexpr int HX = R0;                                      // IQ FIR history (FE_HALO_IQ)
-  // MPX for the MFMA pilot BPF as f16 hi / lo images (history + chunk +
-  // zero slack, natural order), the chunk's last FMX_HIST samples in f32
-  // (stereo history write-back) and the previous chunk's last 32 in f32
-  // (the RDS resampler's window)
-  // (RS = false, process_block's variant, runs no pilot BPF -- k_pilot does
-  // -- and has no images: 10.4 KB less)
-  static constexpr int XW = RS ? FMX_HIST + FE8_T + 32 : 0;
-  static constexpr int MX = HX + FE_HALO_IQ * 8;                     // XH: f16 hi [XW]
-  static constexpr int XLO = MX + XW * 2;                            // XL: f16 lo [XW]
-  // (round 3: no f32 copy of the chunk's last FMX_HIST samples -- the call's
-  // last ones go straight to the history rows in HBM -- so that two k_fe8
-  // workgroups and a k_pll workgroup fit one CU's 160 KB)
-  static constexpr int TL32 = (XLO + XW * 2 + 15) & ~15;             // f32 [32]
+  // the previous chunk's last 32 MPX samples in f32 (the RDS resampler's
+  // window).  No pilot BPF here -- k_pilot runs it after k_fe8, k_frontend
+  // has its own -- so no MPX images; and (round 3) no f32 copy of the chunk's
+  // last FMX_HIST samples: the call's last ones go straight to the history
+  // rows in HBM
+  static constexpr int TL32 = (HX + FE_HALO_IQ * 8 + 15) & ~15;      // f32 [32]
   static constexpr int RS_PAIRS = FMX_NPFB + 1;                      // branch pairs (b, b+1), + the boundary pair
   static constexpr int RS_M = FMX_RDS_RS_SUB + 1;                    // 27 terms (leading / trailing zero)
   static constexpr int RST = (TL32 + 32 * 4 + 15) & ~15;             // RDS resampler bank [33][27] float2
@@ -2765,8 +2679,8 @@ template <int M, int TPP, bool RS = true> struct Fe8Layout {
   static constexpr int SH = SG + 4 * 6 * 8;
   // RS = false (process_block's variant, round 6): the decimator's tap
   // window FmxDesign::dec_q16 (hi, lo: QN entries each) in LDS, read as the
-  // A fragments instead of dec_frag from L2 (RS = true keeps dec_frag: no
-  // LDS to spare beside its images and resampler bank)
+  // A fragments instead of dec_frag from L2 (RS = true keeps dec_frag: it is off
+  // the benchmarked path)
   // Both windows arrive by LDS-DMA behind the first chunk's (whole 64-dword
   // pieces: QDP, QIP; the pad past each window takes copies of its last dword)
   static constexpr int KS = (15 * M + L + 1 + 31) / 32;
@@ -2796,25 +2710,27 @@ template <int M, int TPP, bool RS = true> struct Fe8Layout {
   // LDS-DMA targets (determinism): the early pieces of
   // the next chunk land below uc while the RDS resampler reads uc; the late
   // pieces cover uc only after the barrier that ends its reads, and no piece
-  // reaches the carried images, the resampler bank or the shared words
+  // reaches the IQ FIR history, the resampler's window and bank or the shared
+  // words
   static_assert(NPC_EARLY * 1024 <= UOFF, "early DMA pieces end below uc");
-  static_assert(NPC * 1024 <= HX && HX <= MX && TL32 + 32 * 4 <= RST, "late DMA pieces end below the carried state");
+  static_assert(NPC * 1024 <= HX && HX + FE_HALO_IQ * 8 <= TL32 && TL32 + 32 * 4 <= RST,
+                "late DMA pieces end below the carried state");
   // two k_fe8 workgroups beside a 32 x 8 k_pll workgroup (39168 B): 163840 B per CU
   static_assert(M != 10 || 2 * BYTES + 39168 <= 163840, "two front ends and a k_pll workgroup per CU");
   static_assert(XIN + 4 * IQW * 2 <= YB && (IQW * 2) % 16 == 0 && (FE_HALO_IQ * 2) % 16 == 0,
                 "IQ images below yb, 16-B aligned rows");
 };
 
-// The MFMA FIRs (IQ FIR, pilot BPF) run a P-tap filter as length P8 = P
+// The MFMA FIRs (IQ FIR, k_pilot's pilot BPF) run a P-tap filter as length P8 = P
 // rounded up to 8k + 1 (up to 7 zero taps at the oldest end, same sums), so
 // every K step starts on an 8-sample boundary.
 __device__ __forceinline__ int fir8_len(int P) { return ((P + 6) & ~7) + 1; }
 // register budget: two workgroups (8 waves) per CU beside a k_pll / k_rds /
 // k_rs wave -- <= 168 VGPRs (3 waves per SIMD); M = 8 (the reference's
 // 2.048 MS/s rate) keeps its longer decimator window at 2, and so does the
-// RS = true instance (the resampler and the pilot BPF inside: stage entry
-// points and RDS steps past k_rs's window, never process_block at 240 / 256
-// kHz), which with round 5's per-channel cold start and any-n chunks no
+// RS = true instance (the resampler inside: mono steps and RDS steps past
+// k_rs's window or row geometry, never a stereo + RDS process_block at 240 /
+// 256 kHz on the handle's own rows), which with round 5's per-channel cold start and any-n chunks no
 // longer fits 168 without scratch
 template <int M, int TPP, bool RS>
 #ifndef FMX_FE_PRIO
@@ -2828,8 +2744,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 8 || 
   uint8_t *raw = reinterpret_cast<uint8_t *>(smem);
   float2 *yb = reinterpret_cast<float2 *>(smem + LY::YB);
   float2 *hx = reinterpret_cast<float2 *>(smem + LY::HX);
-  _Float16 *xh = reinterpret_cast<_Float16 *>(smem + LY::MX);  // MPX hi, index FMX_HIST + j
-  _Float16 *xl = reinterpret_cast<_Float16 *>(smem + LY::XLO); // MPX lo
   float *tl32 = reinterpret_cast<float *>(smem + LY::TL32);     // the previous chunk's last 32
   f32x2(*rsb)[LY::RS_M] = reinterpret_cast<f32x2(*)[LY::RS_M]>(smem + LY::RST);
   float *uc = reinterpret_cast<float *>(smem + LY::UOFF); // uc[32 + j]: MPX sample j of the chunk
@@ -2890,7 +2804,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 8 || 
   // loads below: issued before them it costs 26 VGPRs, and vmcnt would make
   // the setup loads wait for it) (16 B per lane, 1-KiB pieces, wave w
   // moving pieces w, w+4, ...): the chunk [n0p*M - L, (n0p + FE8_T)*M) lands
-  // in raw while the previous chunk's pilot FIR and RDS resampler run.
+  // in raw while the previous chunk's RDS resampler runs.
   // Bytes before the row (the first chunk's halo) read 0 (out of range) and
   // are replaced by the carried decimator history.
   const __amdgpu_buffer_rsrc_t riq = make_rsrc(a.iq + (size_t)c * a.iq_stride, (uint32_t)(2L * n * M));
@@ -2912,24 +2826,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 8 || 
   using PAll = std::integral_constant<int, LY::NPC>;
   const int iqL = D->iq_len[par.iqsel];
   const float iqscale = D->iq_scale[par.iqsel];
-  const bool pilot = RS && a.pilot_out != nullptr; // (the launcher never passes a pilot row to RS = false)
-  const bool hist_out = pilot || a.st_hist_out != 0; // the stereo history rows
+  const bool hist_out = a.st_hist_out != 0; // the stereo history rows (k_pilot's and k_pll's)
   const bool rds = a.rds_out != nullptr;
   // rs: the resampler runs here (else k_rs does it, from the MPX and the
   // previous call's window this kernel hands over in rds_win_out)
-  // (RS = true with rds_win_out set: the pilot BPF here, the resampler in
-  // k_rs -- the FMX_FE_PILOT A/B)
   const bool rs = RS && rds && a.rds_win_out == nullptr;
   const float dc_a1 = -1.0f + 0.0005f; // iirfilt_rrrf_create_dc_blocker(0.0005)
   const float dc_c = -dc_a1;
   const float *su = reinterpret_cast<const float *>(smem + LY::SU); // RS = false: the landed words
 
-  // ---- zeroed images, carried state ----
-  for (int h = tid; h < LY::XW / 2; h += 256) {
-    reinterpret_cast<uint32_t *>(xh)[h] = 0u;
-    reinterpret_cast<uint32_t *>(xl)[h] = 0u;
-  }
-  if (RS) __syncthreads();
+  // ---- carried state ----
   if (RS) {
     for (int h = tid; h < FE_HALO_IQ; h += 256) {
       const float2_t v = a.iq_hist[(size_t)c * (FMX_IQ_MAXLEN - 1) + h];
@@ -2947,16 +2853,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 8 || 
     sh->clip = 0;
   }
   FE_SETUP_STAMP(1)
-  if (RS) {
-    const float *hist = a.st_hist_rd + (size_t)c * FMX_HIST;
-    for (int h = tid; h < FMX_HIST; h += 256) {
-      const float v = pilot ? hist[h] : 0.0f;
-      const _Float16 hv = (_Float16)v;
-      xh[h] = hv;
-      xl[h] = (_Float16)(v - (float)hv);
-    }
-  }
-  FE_SETUP_STAMP(2)
   float agc_g = 1.0f, agc_y2p = 1.0f;
   if (RS && par.agc != 0 && tid == 0) {
     agc_g = a.agc[2 * c];
@@ -3404,12 +3300,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 8 || 
         const float im = p.x * r.y - p.y * r.x;
         const float m = fmx_atan2f(im, re) * ref; // select-free (fmx_math.h)
         mv[k] = m;
-        // f16 hi / lo split for the MFMA pilot BPF (m = hi + lo to 22 bits)
-        if (pilot) {
-          const _Float16 hv = (_Float16)m;
-          xh[FMX_HIST + j] = hv;
-          xl[FMX_HIST + j] = (_Float16)(m - (float)hv);
-        }
         if (a.mpx_out && j < cnt) a.mpx_out[(size_t)c * a.mpx_stride + n0 + j] = m;
       }
       if (tid == 0) {
@@ -3502,71 +3392,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 8 || 
       if (rds && tid < 32) a.rds_hist[(size_t)c * 32 + tid] = uc[cnt + tid];
     }
     if (rs && tid < 32) tl32[tid] = uc[cnt + tid];
-    __syncthreads(); // uc is dead: the rest of the next chunk may land (behind the pilot FIR)
+    __syncthreads(); // uc is dead: the rest of the next chunk may land
     if (n0 + cnt < n) dma_chunk(n0 + cnt, PEarly{}, PAll{});
     if (rs) e_pos = sh->e_end;
     FE_STAMP(5)
-    // ================= 19 kHz pilot band-pass =================
-    if (pilot) {
-      // v_mfma_f32_16x16x32_f16 tiles as the decimator's: 16 outputs (rows,
-      // A = taps) of 16 blocks of 16 outputs (columns, B = MPX), K = the
-      // block's P8 + 15 inputs from x[16 B - P8 + 1]; B from the hi / lo
-      // images (two 16-B reads), A fragments (FmxDesign::pilot_frag, tap *
-      // 2^12 as hi + lo) from global memory, one K step ahead; three MFMAs
-      // per K step (hi*hi, hi*lo, lo*hi).  Each wave: two tiles, 512 outputs.
-      typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-      typedef float f32x4_t __attribute__((ext_vector_type(4)));
-      const int P8 = fir8_len(D->pilot_len);
-      const int KSP = D->pilot_ks;
-      const int col = lane & 15, g = lane >> 4;
-      const int xb = FMX_HIST + 16 * (32 * wave + col) - (P8 - 1) + 8 * g; // 8-aligned: P8 = 8k + 1
-      const f16x8_t *bh = reinterpret_cast<const f16x8_t *>(xh + xb);
-      const f16x8_t *bl = reinterpret_cast<const f16x8_t *>(xl + xb);
-      const u32x4 *fa = reinterpret_cast<const u32x4 *>(&D->pilot_frag[0][0][0][0]) + lane;
-      const __amdgpu_buffer_rsrc_t prow = make_rsrc(a.pilot_out + (size_t)c * a.pilot_stride, 4u * (uint32_t)n);
-      f32x4_t pacc[2];
-      pacc[0] = pacc[1] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
-      u32x4 ah = fa[0], al = fa[64];
-      for (int ks = 0; ks < KSP; ++ks) {
-        const f16x8_t ahi = __builtin_bit_cast(f16x8_t, ah), alo = __builtin_bit_cast(f16x8_t, al);
-        if (ks + 1 < KSP) {
-          ah = fa[128 * (ks + 1)];
-          al = fa[128 * (ks + 1) + 64];
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const f16x8_t xhi = bh[32 * u + 4 * ks], xlo = bl[32 * u + 4 * ks]; // + 256 u + 32 ks samples
-          pacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, xhi, pacc[u], 0, 0, 0);
-          pacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, xlo, pacc[u], 0, 0, 0);
-          pacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, xhi, pacc[u], 0, 0, 0);
-        }
-      }
-      constexpr float kInv = 1.0f / 4096.0f;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        // lane: outputs 256 (2 wave + u) + 16 col + 4 g + i, i = 0..3, as a
-        // buffer store over the call's row: outputs past n (a shorter last
-        // chunk; cnt is a multiple of 4) are dropped by the range check, no branch
-        const int o = n0 + 256 * (2 * wave + u) + 16 * col + 4 * g;
-        const u32x4 pv = u32x4{__builtin_bit_cast(uint32_t, pacc[u][0] * kInv), __builtin_bit_cast(uint32_t, pacc[u][1] * kInv),
-                               __builtin_bit_cast(uint32_t, pacc[u][2] * kInv), __builtin_bit_cast(uint32_t, pacc[u][3] * kInv)};
-        __builtin_amdgcn_raw_buffer_store_b128(pv, prow, 4u * (uint32_t)o, 0, 0);
-      }
-    }
-    FE_STAMP(4)
-    // ================= carry halos to the next chunk =================
-    // (RS = false has no images; nothing after the "uc is dead" barrier reads
-    // LDS there, so the next chunk needs no barrier here)
-    if (RS) {
-      // the chunk's last FMX_HIST samples become the f16 images' history
-      static_assert(FMX_HIST == 2 * 256, "one f16 pair per thread");
-      const uint32_t ch = reinterpret_cast<const uint32_t *>(xh)[cnt / 2 + tid];
-      const uint32_t cl = reinterpret_cast<const uint32_t *>(xl)[cnt / 2 + tid];
-      __syncthreads();
-      reinterpret_cast<uint32_t *>(xh)[tid] = ch;
-      reinterpret_cast<uint32_t *>(xl)[tid] = cl;
-      __syncthreads();
-    }
+    // ================= end of the chunk =================
+    // RS = true: every wave is past this chunk's LDS (hx, uc, tl32, e_end)
+    // before the next one starts -- the barrier the f16 MPX images' carry
+    // stood behind while this instance ran the pilot BPF.  (RS = false reads
+    // no LDS after the "uc is dead" barrier, so the next chunk needs none.)
+    if (RS) __syncthreads();
   }
 
   // ---- write back state ----
@@ -3641,9 +3476,10 @@ template <int M, int TPP, bool RS> static int fe8_launch_rs(const FeArgs &a, hip
   return fmx_launch(k_fe8<M, TPP, RS>, dim3(a.C), dim3(256), smem, st, a);
 }
 // the resampler in the kernel, or (rds_win_out set) left to k_rs
-// (process_block's variant, RS = false, has no pilot BPF: k_pilot runs it)
+// (k_fe8 has no pilot BPF: k_pilot runs it after a process_block step's)
 template <int M, int TPP> static int fe8_launch(const FeArgs &a, hipStream_t st) {
-  if (a.rds_out && a.rds_win_out && !a.pilot_out) return fe8_launch_rs<M, TPP, false>(a, st);
+  if (a.pilot_out) return FMX_E_INVALID;
+  if (a.rds_out && a.rds_win_out) return fe8_launch_rs<M, TPP, false>(a, st);
   return fe8_launch_rs<M, TPP, true>(a, st);
 }
 
@@ -3668,19 +3504,18 @@ template <int M, int TPP, bool VEC> static int fe_launch(const FeArgs &a, hipStr
 // explicit launchers so fmx_capi can pick the instantiation.
 namespace fmx {
 // steady state: whole 2048-sample chunks, full history, no complex
-// decimator output, 16-B pilot rows, RDS rate ratio < 0.9 (<= 8 resampler
-// outputs per thread and chunk) -> k_fe8
+// decimator output, RDS rate ratio < 0.9 (<= 8 resampler outputs per thread
+// and chunk) -> k_fe8
 // k_fe8 takes any call of n >= FE8_MIN_N samples with n % 4 == 0 (chunks
 // of one size, a multiple of 8, see k_fe8: the last chunk's length is n mod
-// 8 off a multiple of 8, and its 16-B pilot stores and f16-pair history carry
-// need a multiple of 4) on 16-B aligned IQ rows, cold or warm decimator
+// 8 off a multiple of 8; the chunks are whole groups of 4 samples) on 16-B
+// aligned IQ rows, cold or warm decimator
 // history per channel; other n (e.g. 1025 at M = 8, where every n passes the
 // IQ alignment test) take k_frontend
 static bool fe8_ok(const FeArgs &a, int M) {
   if (a.in_mode != FE_IN_U8_DECIM) return false;
   const bool aligned = ((((uintptr_t)a.iq) | (uintptr_t)a.iq_stride) & 15) == 0 && ((2L * a.n * M) & 15) == 0;
   return aligned && a.n >= FE8_MIN_N && (a.n & 3) == 0 && a.do_demod && !a.bb_out &&
-         (!a.pilot_out || ((((uintptr_t)a.pilot_out) | (uintptr_t)a.pilot_stride * 4) & 15) == 0) &&
          a.des_fs >= 190000;
 }
 bool frontend_is_fe8(const FeArgs &a, int M, int tpp) {
@@ -3714,16 +3549,8 @@ int launch_pll(const PllArgs &a, void *stream) {
   // (PllArgs::n_cu, queried once per handle at create)
   const int n_cu = a.n_cu > 0 ? a.n_cu : 256;
   hipStream_t st = static_cast<hipStream_t>(stream);
-#ifndef FMX_PLL_CH_FORCE // A/B variants only
   const int ch = 2 * ((a.C + 15) / 16) <= n_cu ? 16 : 24;
-#else
-  const int ch = FMX_PLL_CH_FORCE;
-#endif
   if (ch == 16) return fmx_launch(k_pll<16>, dim3((a.C + 15) / 16), dim3(64 * PLL_WAVES(16)), 0, st, a);
-#if defined(FMX_PLL_CH_FORCE) && FMX_PLL_CH_FORCE != 16 && FMX_PLL_CH_FORCE != 24
-  return fmx_launch(k_pll<FMX_PLL_CH_FORCE>, dim3((a.C + FMX_PLL_CH_FORCE - 1) / FMX_PLL_CH_FORCE),
-                    dim3(64 * PLL_WAVES(FMX_PLL_CH_FORCE)), 0, st, a);
-#endif
   return fmx_launch(k_pll<24>, dim3((a.C + 23) / 24), dim3(64 * PLL_WAVES(24)), 0, st, a);
 }
 int launch_audio(const AudioArgs &a, void *stream) {
@@ -3732,23 +3559,20 @@ int launch_audio(const AudioArgs &a, void *stream) {
 /* ================================================================== */
 /* k_pilot: the 19 kHz pilot band-pass (stereo_decoder.cpp:229-230)    */
 /* ================================================================== */
-/* k_fe8's pilot stage as its own kernel on the front-end stream, after
- * k_fe8 (which then writes only the MPX and the stereo history rows).  In
- * k_fe8 the stage waited on one tap-fragment load per K step with two
- * workgroups (8 waves) per CU to hide it; here a workgroup is 6.3 KB of LDS
- * and 4 small waves, so many are resident and the loads overlap.  The sums
- * are k_fe8's: the same f16 hi / lo images of the same samples, the same
- * 8-aligned windows, the same three MFMAs per K step in the same order
- * (a tile of 256 outputs starts on a 256-sample boundary in both).
+/* The pilot stage k_fe8 had up to round 3, as its own kernel on the
+ * front-end stream, after k_fe8 (which writes only the MPX and the stereo
+ * history rows).  In k_fe8 the stage waited on one tap-fragment load per K
+ * step with two workgroups (8 waves) per CU to hide it; here a workgroup is
+ * small, so many are resident and the loads overlap.  The sums are f16 hi /
+ * lo images of the MPX samples on 8-aligned windows, three MFMAs per K step
+ * (hi*hi, hi*lo, lo*hi); a tile of 256 outputs starts on a 256-sample
+ * boundary.
  * Workgroup = 4096 outputs of one channel (4 waves x 4 tiles of 16 x 16:
  * the fragments, 22 KB per K sweep from L2, are loaded once per 4 tiles); the
  * block -> (channel, segment) map keeps a channel's segments on one XCD, so
  * the window halo a neighbour loaded is an L2 hit. */
 #define PIL_TPW 4                  // 256-output tiles per wave: one tap-fragment load feeds PIL_TPW MFMA chains
 #define PIL_SEG (4 * 256 * PIL_TPW) // outputs per workgroup
-#ifndef FMX_PILOT_QLDS
-#define FMX_PILOT_QLDS 1 // A fragments from the LDS tap window (round 6; 0: pilot_frag from L2, A/B)
-#endif
 #define PIL_QP ((2 * FMX_PILOT_QN + 63) / 64) // 64-dword pieces of the [2][2][FMX_PILOT_QN] u16 window
 struct PilLds {
   // sample s0 - FMX_HIST + i at [i]: the history (previous call's MPX rows
@@ -3758,7 +3582,7 @@ struct PilLds {
   _Float16 xl[FMX_HIST + PIL_SEG + 32] __attribute__((aligned(16)));
   // the tap window FmxDesign::pilot_q16 ([copy][hi, lo][entry]; whole 64-dword
   // LDS-DMA pieces, the pad past it copies of its last dword)
-  uint32_t q[FMX_PILOT_QLDS ? PIL_QP * 64 : 1] __attribute__((aligned(16)));
+  uint32_t q[PIL_QP * 64] __attribute__((aligned(16)));
 };
 #ifndef FMX_PILOT_PRIO
 #define FMX_PILOT_PRIO 0 // k_pilot's wave priority (s_setprio) beside the other streams' waves
@@ -3782,7 +3606,7 @@ __global__ __launch_bounds__(256) void k_pilot(PilotArgs a) {
   const int KSP = D->pilot_ks;
   const float *mrow = a.mpx + (size_t)c * a.mpx_stride;
   const float *hrow = a.st_hist_rd + (size_t)c * FMX_HIST + FMX_HIST; // hrow[s], s < 0
-  if (FMX_PILOT_QLDS) { // the tap window by LDS-DMA, ahead of the image loads (it lands before their wait)
+  { // the tap window by LDS-DMA, ahead of the image loads (it lands before their wait)
     static_assert(FMX_PILOT_QN % 2 == 0, "dword window");
     const float *qs = reinterpret_cast<const float *>(&D->pilot_q16[0][0][0]);
     for (int p = wave; p < PIL_QP; p += 4)
@@ -3821,22 +3645,21 @@ __global__ __launch_bounds__(256) void k_pilot(PilotArgs a) {
     *reinterpret_cast<f16x4_t *>(&L.xh[i]) = hv;
     *reinterpret_cast<f16x4_t *>(&L.xl[i]) = lv;
   }
-  if (FMX_PILOT_QLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the window's moves landed (before the barrier)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the window's moves landed (before the barrier)
   __syncthreads();
-  // tiles PIL_TPW w + u: 16 outputs (rows, A = taps, FmxDesign::pilot_frag)
+  // tiles PIL_TPW w + u: 16 outputs (rows, A = taps, from the LDS tap window:
+  // round 6; FmxDesign::pilot_frag from L2 before)
   // of 16 blocks of 16 outputs (columns, B = MPX), K = P8 + 15 inputs
   const int col = lane & 15, g = lane >> 4;
   const int xb = FMX_HIST + 256 * PIL_TPW * wave + 16 * col - (P8 - 1) + 8 * g;
   const f16x8_t *bh = reinterpret_cast<const f16x8_t *>(&L.xh[xb]);
   const f16x8_t *bl = reinterpret_cast<const f16x8_t *>(&L.xl[xb]);
-  const u32x4 *fa = reinterpret_cast<const u32x4 *>(&D->pilot_frag[0][0][0][0]) + lane;
-  // (FMX_PILOT_QLDS) this lane's 8 window entries from 32 ks + 8 g + 15 - col:
+  // this lane's 8 window entries from 32 ks + 8 g + 15 - col:
   // in copy (15 - col) & 1 they start on an even entry, four dwords
   const int qb = 8 * g + 15 - col, qc = qb & 1;
   const uint32_t *qh = &L.q[0] + qc * FMX_PILOT_QN + (qb - qc) / 2;
   const uint32_t *ql = qh + FMX_PILOT_QN / 2;
   auto frag = [&](int ks, int s) __attribute__((always_inline)) {
-    if (!FMX_PILOT_QLDS) return fa[128 * ks + 64 * s];
     const uint32_t *q = (s ? ql : qh) + 16 * ks;
     return u32x4{q[0], q[1], q[2], q[3]};
   };
@@ -3999,13 +3822,7 @@ int launch_rds_sym(const RdsArgs &a, void *stream) {
   // two k_fe8 workgroups (2 x 62.5 KB) leave 35 KB of a CU's 160 KB: several
   // k_rds workgroups fit beside them
   static_assert(sizeof(RdsLds) <= 16 * 1024, "k_rds LDS");
-  static_assert(RDS_FOFF + sizeof(RdsFusedLds) <= 28 * 1024, "fused k_rds LDS");
-#if FMX_RDS_FUSED
-  if (a.fused)
-    return fmx_launch(k_rds<true>, dim3((a.C + RDS_CPW - 1) / RDS_CPW), dim3(64), RDS_FOFF + sizeof(RdsFusedLds),
-                      static_cast<hipStream_t>(stream), a);
-#endif
-  return fmx_launch(k_rds<false>, dim3((a.C + RDS_CPW - 1) / RDS_CPW), dim3(64), sizeof(RdsLds), static_cast<hipStream_t>(stream), a);
+  return fmx_launch(k_rds, dim3((a.C + RDS_CPW - 1) / RDS_CPW), dim3(64), sizeof(RdsLds), static_cast<hipStream_t>(stream), a);
 }
 int launch_bits(const RdsArgs &a, void *stream) {
   static_assert(sizeof(BitsLds) <= 16 * 1024, "k_bits LDS");

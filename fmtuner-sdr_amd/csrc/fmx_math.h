@@ -73,44 +73,23 @@ FMX_HD uint32_t fmx_nco_constrain_ref(float x) {
   return (s >= 4294967296.0f) ? 0u : fmx_cvt_u32(s);
 }
 
-// Forms of the stereo PLL's sine / constrain arithmetic (k_pll), chosen at
-// compile time; the shipped library is built with the defaults and
-// tests/hip/libpllmath.so sweeps whatever forms it is built with.  Round 6
-// A/B (profiles/r06a_*): see DESIGN.md section 3.
-//   FMX_PLL_CHAIN  W0's feedback sine of the word:
-//     0  round 5: the word's top 23 bits truncated (v_alignbit_b32 into a
-//        float in [1, 2)), one op; a phase bias of up to -2^-23 turn
-//     1  the same with the word carried +256 by W0 (FMX_CHAIN_TOFF): the top
-//        23 bits rounded to nearest, still one op
-//     2  round 4: (float)(int32)theta 2^-32, a signed 24-bit turn (two ops)
-//     3  (float)(uint32)theta 2^-32: the reference's own rounding of the word
-//        ((float)theta in nco_crcf_get_phase, as oracle Nco::get_phase) (two ops)
-//   FMX_WORD_SINCOS  the P waves' sine / cosine of the word (vcoI / vcoQ,
-//     cos 2 phase): 0 signed 24-bit turn, 1 (float)(uint32)theta as the reference
-//   FMX_PLL_WORDS  pll_step's constrain words: 0 truncating converts (e < 0:
-//     within 130 / 144 words of the reference's 256-word steps); 1 e < 0
-//     rounded to the reference's 256-word grid by one f32 add of 2^32
-//     (saturating converts, no compare; e >= 0 one word low); 3 the alpha
-//     (frequency) word as 1, the beta (phase) word as 0
-// Shipped (round 6): FMX_PLL_CHAIN 1 (free: removes the -3.7e-7 rad phase
-// bias of the truncated sine) and FMX_PLL_WORDS 3 (the frequency word as the
-// reference rounds it: worst PCM RMS against the oracle 3.6e-6 -> 1.4e-6,
-// median 9.3e-7 -> 4.3e-7, for +1.1 % / +1.5 % step time at 4096 / 2048
-// channels; profiles/r06c_*, r06d_*).  The sine forms alone move no PCM error.
-#ifndef FMX_PLL_CHAIN
-#define FMX_PLL_CHAIN 1
-#endif
-#ifndef FMX_WORD_SINCOS
-#define FMX_WORD_SINCOS 0
-#endif
-#ifndef FMX_PLL_WORDS
-#define FMX_PLL_WORDS 3
-#endif
-#if FMX_PLL_CHAIN == 1
+// The stereo PLL's sine / constrain arithmetic (k_pll), as shipped since round
+// 6 (tests/hip/libpllmath.so sweeps it, tests/test_gpu_pllmath.py pins it):
+//   - W0's feedback sine takes the word's top 23 bits rounded to nearest: the
+//     word is carried + FMX_CHAIN_TOFF by W0 and truncated by one
+//     v_alignbit_b32 (free against plain truncation, and without its -3.7e-7
+//     rad phase bias);
+//   - the P waves' sine / cosine of the word (vcoI / vcoQ, cos 2 phase) take
+//     it as a signed 24-bit turn;
+//   - pll_step's alpha (frequency) word is rounded to the reference's 256-word
+//     grid, its beta (phase) word is a truncating convert: worst PCM RMS
+//     against the oracle 3.6e-6 -> 1.4e-6, median 9.3e-7 -> 4.3e-7, for +1.1 %
+//     / +1.5 % step time at 4096 / 2048 channels (profiles/r06c_*, r06d_*).
+// The forms that lost (a converted and scaled word for either sine, both
+// constrain words truncated or both rounded) are in DESIGN.md section 3 and
+// its performance log (profiles/r06a_*); the sine forms alone move no PCM
+// error.
 #define FMX_CHAIN_TOFF 256u
-#else
-#define FMX_CHAIN_TOFF 0u
-#endif
 
 #ifdef __HIPCC__
 // The stereo PLL's feedback chain (k_pll W0, stereo_decoder.cpp:178-192), one
@@ -123,32 +102,20 @@ FMX_HD uint32_t fmx_nco_constrain_ref(float x) {
 // tests/golden/pllmath_gpu.json).
 //
 // fmx_chain_sin(theta + FMX_CHAIN_TOFF) = sin(2 pi theta / 2^32): v_sin_f32
-// takes turns.  Forms 0 / 1: the word's top 23 bits become the mantissa of a
-// float in [1, 2) with one v_alignbit_b32 ({0x7F, w} >> 9 = 0x3F800000 | w >>
-// 9), so sin(2 pi (1 + w / 2^32)) = sin(2 pi w / 2^32) up to the dropped 9
-// bits and v_sin's own error -- truncated (form 0), or rounded when the word
-// is carried + 256 (form 1).  Forms 2 / 3 convert and scale.
+// takes turns.  The word's top 23 bits become the mantissa of a float in
+// [1, 2) with one v_alignbit_b32 ({0x7F, w} >> 9 = 0x3F800000 | w >> 9), so
+// sin(2 pi (1 + w / 2^32)) = sin(2 pi w / 2^32) up to the dropped 9 bits --
+// rounded, the word being carried + 256 -- and v_sin's own error.
 __device__ __forceinline__ float fmx_chain_sin(uint32_t w) {
-#if FMX_PLL_CHAIN == 2
-  return __builtin_amdgcn_sinf((float)(int32_t)w * 2.3283064365386963e-10f);
-#elif FMX_PLL_CHAIN == 3
-  return __builtin_amdgcn_sinf((float)w * 2.3283064365386963e-10f);
-#else
   return __builtin_amdgcn_sinf(__builtin_bit_cast(float, __builtin_amdgcn_alignbit(0x7Fu, w, 9u)));
-#endif
 }
 // fmx_word_sincos: sine and cosine of an NCO word (phase 2 pi theta / 2^32)
-// by v_sin / v_cos, which take turns: form 0 the word as a signed fraction of
-// a turn in [-0.5, 0.5) (rounded to 24 bits: < 2^-25 turn), form 1 as
-// (float)theta 2^-32 in [0, 1], the reference's rounding of the word.
+// by v_sin / v_cos, which take turns: the word as a signed fraction of a turn
+// in [-0.5, 0.5) (rounded to 24 bits: < 2^-25 turn).
 // k_pll's outputs (vcoI / vcoQ of the pilot I/Q, cos 2 phase of the L-R mix,
 // stereo_decoder.cpp:178-180,194-195,218-220), swept with the chain.
 __device__ __forceinline__ void fmx_word_sincos(uint32_t theta, float *s, float *c) {
-#if FMX_WORD_SINCOS == 1
-  const float r = (float)theta * 2.3283064365386963e-10f;
-#else
   const float r = (float)(int32_t)theta * 2.3283064365386963e-10f;
-#endif
   *s = __builtin_amdgcn_sinf(r);
   *c = __builtin_amdgcn_cosf(r);
 }
@@ -161,58 +128,34 @@ __device__ __forceinline__ uint32_t fmx_cvt_u32_sat(float x) {
 }
 // fmx_chain_words: the two constrain words of pll_step from the pilot's
 // pre-products pa = pilot alpha/2pi 2^32, pb = pilot beta/2pi 2^32 (one packed
-// multiply by vcoQ).  Form 0, truncating converts: for |e k| < 1/2 the word
-// constrain(e k) = frac(e k / 2 pi) 2^32 equals (uint32)(int32)(e k / 2 pi 2^32)
-// up to the float roundings (and, for e < 0, the reference's rounding of
-// 1 + frac to 24 bits), which the sweep bounds.  Form 1: x = e k / 2 pi 2^32
-// as two saturating converts, cvt(x) + cvt(x + 2^32): for x < 0 the first is
-// 0 and the second the f32 sum 2^32 + x rounded to the 256-word grid, which
-// is the reference's (float)(fpart + 1) 2^32; for x >= 0 the second
-// saturates to 2^32 - 1, so the word is trunc(x) - 1.
-// (form 3: the alpha word as form 1, the beta word as form 0)
+// multiply by vcoQ), x = e k / 2 pi 2^32.  The beta word is a truncating
+// convert: for |e k| < 1/2 the word constrain(e k) = frac(e k / 2 pi) 2^32
+// equals (uint32)(int32)x up to the float roundings (and, for e < 0, the
+// reference's rounding of 1 + frac to 24 bits), which the sweep bounds.  The
+// alpha word is two saturating converts, cvt(x) + cvt(x + 2^32): for x < 0 the
+// first is 0 and the second the f32 sum 2^32 + x rounded to the 256-word
+// grid, which is the reference's (float)(fpart + 1) 2^32; for x >= 0 the
+// second saturates to 2^32 - 1, so the word is trunc(x) - 1.
 __device__ __forceinline__ void fmx_chain_words(float pa, float pb, float vcoQ, uint32_t *ca, uint32_t *cb) {
   typedef float f2 __attribute__((ext_vector_type(2)));
   const f2 x = f2{pa, pb} * f2{vcoQ, vcoQ};
-#if FMX_PLL_WORDS == 1
-  const f2 y = x + f2{4294967296.0f, 4294967296.0f};
-  *ca = fmx_cvt_u32_sat(x.x) + fmx_cvt_u32_sat(y.x);
-  *cb = fmx_cvt_u32_sat(x.y) + fmx_cvt_u32_sat(y.y);
-#elif FMX_PLL_WORDS == 3
   *ca = fmx_cvt_u32_sat(x.x) + fmx_cvt_u32_sat(x.x + 4294967296.0f);
   *cb = (uint32_t)(int32_t)x.y;
-#else
-  *ca = (uint32_t)(int32_t)x.x;
-  *cb = (uint32_t)(int32_t)x.y;
-#endif
 }
 // fmx_chain_step: one sample's pll_step + step on the carried words, with
 // the words of fmx_chain_words: dtheta += ca; theta += dtheta(new) + cb --
 // the reference's order (pll_step adds ca to dtheta and cb to theta, step
 // then adds the updated dtheta), so that theta's update is one v_add3_u32 of
-// the updated dtheta and no theta + dtheta is formed.  Form 1 / 3 sum the
-// saturating converts straight into dtheta with v_add3_u32.
+// the updated dtheta and no theta + dtheta is formed.  The alpha word's two
+// saturating converts are summed straight into dtheta with v_add3_u32.
 __device__ __forceinline__ void fmx_chain_step(float pa, float pb, float vcoQ, uint32_t &theta, uint32_t &dtheta) {
   typedef float f2 __attribute__((ext_vector_type(2)));
   const f2 x = f2{pa, pb} * f2{vcoQ, vcoQ};
   uint32_t tn;
-#if FMX_PLL_WORDS == 1
-  const f2 y = x + f2{4294967296.0f, 4294967296.0f};
-  const uint32_t a0 = fmx_cvt_u32_sat(x.x), a1 = fmx_cvt_u32_sat(y.x);
-  const uint32_t b0 = fmx_cvt_u32_sat(x.y), b1 = fmx_cvt_u32_sat(y.y);
-  asm("v_add3_u32 %0, %1, %2, %3" : "=v"(dtheta) : "v"(dtheta), "v"(a0), "v"(a1));
-  uint32_t s;
-  asm("v_add3_u32 %0, %1, %2, %3" : "=v"(s) : "v"(theta), "v"(dtheta), "v"(b0));
-  tn = s + b1;
-#elif FMX_PLL_WORDS == 3
   const uint32_t a0 = fmx_cvt_u32_sat(x.x), a1 = fmx_cvt_u32_sat(x.x + 4294967296.0f);
   const uint32_t cb = (uint32_t)(int32_t)x.y;
   asm("v_add3_u32 %0, %1, %2, %3" : "=v"(dtheta) : "v"(dtheta), "v"(a0), "v"(a1));
   asm("v_add3_u32 %0, %1, %2, %3" : "=v"(tn) : "v"(theta), "v"(dtheta), "v"(cb));
-#else
-  const uint32_t ca = (uint32_t)(int32_t)x.x, cb = (uint32_t)(int32_t)x.y;
-  dtheta += ca;
-  asm("v_add3_u32 %0, %1, %2, %3" : "=v"(tn) : "v"(theta), "v"(dtheta), "v"(cb));
-#endif
   theta = tn;
 }
 #endif

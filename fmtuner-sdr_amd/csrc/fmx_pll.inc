@@ -18,9 +18,6 @@
 #ifndef PLL_PUNROLL
 #define PLL_PUNROLL 8                      // P waves' loop unroll (a multiple of every ring size; 1: not unrolled)
 #endif
-#ifndef PLL_FMAC_DPP
-#define PLL_FMAC_DPP 1                     // stage A's scans as v_fmac_f32_dpp (else v_mov_dpp + v_fmac)
-#endif
 template <int CH> struct alignas(16) PllShared {
   static_assert(CH % 4 == 0 && CH * PLL_T == 64 * PLL_NPW(CH), "one item per P-wave lane");
   float inp[PLL_NINP][CH][PLL_T];      // pilot tiles (LDS-DMA by the P waves)
@@ -47,12 +44,9 @@ __device__ __forceinline__ void pll_matrix(float delayed, float cos2, float *mon
   *dr = sr - monoNorm;
 }
 
-// DPP within the 16-lane row of a channel: row_shr:d (lanes t < d read 0)
-// and row_ror:1 (lane t reads t - 1, lane 0 reads lane 15)
-template <int D> __device__ __forceinline__ float pll_shr(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x110 + D, 0xF, 0xF, true));
-}
-// lane 15 of the channel's row to all 16 lanes (DPP row_newbcast:15, gfx90a+)
+// DPP within the 16-lane row of a channel: lane 15 of the row to all 16 lanes
+// (row_newbcast:15, gfx90a+) and row_ror:1 (lane t reads t - 1, lane 0 reads
+// lane 15)
 __device__ __forceinline__ float pll_bcast15(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x15F, 0xF, 0xF, false));
 }
@@ -435,11 +429,7 @@ __global__ __launch_bounds__(64 * PLL_WAVES(CH)) __attribute__((amdgpu_waves_per
         pll_matrix(delayed, c2B, &mo, &dl, &dr);
         const float ol = mo + (dl * blend);
         const float orr = mo + (dr * blend);
-#ifdef FMX_AB_NO_LR // A/B only: the stores are issued but dropped (no raw L/R bytes move)
-        const uint32_t off = 0xFFFFFFFFu;
-#else
         const uint32_t off = (chv && jb * PLL_T + tt < n) ? 4u * (uint32_t)(lrJ * jb + lr_off) : 0xFFFFFFFFu;
-#endif
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, ol), lbr, off, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, orr), rbr, off, 0, 0);
       }
@@ -468,10 +458,9 @@ __global__ __launch_bounds__(64 * PLL_WAVES(CH)) __attribute__((amdgpu_waves_per
         // carry of the previous tile's last sample
         float x0 = fabsf(pilot) * kI, x1 = fabsf(mpx) * kI;
         float x2 = (pilot * cP) * kI, x3 = (pilot * sP) * kI;
-#if PLL_FMAC_DPP
         // one v_fmac_f32 with the row shift on its first source per step:
         // x += shr(x) k (lanes t < d read 0; the same single-rounding fma as
-        // below, round 4 r04as).  The four chains interleave, so a value is
+        // a v_mov_dpp + v_fmac pair, round 4 r04as).  The four chains interleave, so a value is
         // read by DPP three VALU ops after its write; the s_nop covers the
         // values the compiler wrote right before the block (VALU write -> DPP
         // read: two wait states)
@@ -488,18 +477,6 @@ __global__ __launch_bounds__(64 * PLL_WAVES(CH)) __attribute__((amdgpu_waves_per
                      : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3)
                      : "v"(k1), "v"(k2), "v"(k4), "v"(k8));
 #undef PLL_FD
-#else
-#define PLL_SCAN_STEP(DD, KD)          \
-  x0 = fmaf(KD, pll_shr<DD>(x0), x0);  \
-  x1 = fmaf(KD, pll_shr<DD>(x1), x1);  \
-  x2 = fmaf(KD, pll_shr<DD>(x2), x2);  \
-  x3 = fmaf(KD, pll_shr<DD>(x3), x3);
-        PLL_SCAN_STEP(1, k1)
-        PLL_SCAN_STEP(2, k2)
-        PLL_SCAN_STEP(4, k4)
-        PLL_SCAN_STEP(8, k8)
-#undef PLL_SCAN_STEP
-#endif
         const float o0 = cr0, o1 = cr1, o2 = cr2, o3 = cr3;
         const float pbm = fmaf(kp1, o0, x0);
         const float mm = fmaf(kp1, o1, x1);

@@ -127,8 +127,9 @@ extern "C" {
 // out[7]: mean |chain-sine error|, out[8]: words swept; out[9..14]: word
 // maxima (see k_words), out[15]: (pilot, vcoQ) pairs checked, out[16]: the
 // chain sine's mean phase error (radians, see k_sine), out[17..19]: the forms
-// built (FMX_PLL_CHAIN, FMX_WORD_SINCOS, FMX_PLL_WORDS), out[20..21]: the
-// mean |d ca| / |d cb| over the e < 0 pairs.  Returns 0, or a negative HIP
+// of fmx_math.h by their round-6 numbers (chain sine 1, word sine / cosine 0,
+// constrain words 3: the only ones left), out[20..21]: the mean |d ca| /
+// |d cb| over the e < 0 pairs.  Returns 0, or a negative HIP
 // error.
 int pllmath_sweep(float alpha, float beta, double *out, int nout) {
   if (nout < 22) return -100;
@@ -166,9 +167,9 @@ int pllmath_sweep(float alpha, float beta, double *out, int nout) {
   for (int k = 0; k < 6; ++k) out[9 + k] = f(kNS + k);
   out[15] = (double)nb * 2.0 * nvq;
   out[16] = sums[2] / 2147483648.0;
-  out[17] = FMX_PLL_CHAIN;
-  out[18] = FMX_WORD_SINCOS;
-  out[19] = FMX_PLL_WORDS;
+  out[17] = 1;
+  out[18] = 0;
+  out[19] = 3;
   out[20] = sums[3] / ((double)nb * nvq); // e < 0: half of the 2 nb nvq pairs
   out[21] = sums[4] / ((double)nb * nvq);
   return 0;

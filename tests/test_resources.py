@@ -98,7 +98,9 @@ def test_pilot_kernel_budget(tmp_path):
 
 def test_rds_fits_beside_two_front_ends(tmp_path):
     ks = _kernels(tmp_path)
-    for name, f in _find(ks, r"5k_rdsILb0E").items():
+    hits = _find(ks, r"5k_rdsENS_7RdsArgs")
+    assert len(hits) == 1, sorted(hits)
+    for name, f in hits.items():
         assert f.get("vgpr_count", 0) + f.get("agpr_count", 0) <= 512 - 2 * 168, (name, f)
         assert f.get("vgpr_spill_count", 0) == 0, (name, f)
 

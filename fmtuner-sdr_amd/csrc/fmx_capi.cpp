@@ -1897,6 +1897,175 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
   return stage_end(h);
 }
 
+/* ---- wideband channelizer (fmx.h; design in fmx_wb_design.cpp, kernel in fmx_wb.inc) ---- */
+namespace {
+struct Wb {
+  Handle *h = nullptr;
+  WbPlan p;
+  int C = 0;
+  uint16_t *d_w = nullptr;    // [C][4][Lp] weight rows
+  uint32_t *d_fpos = nullptr; // [C] f mod Fs
+  void *d_hist[2] = {};       // the last L - 1 raw samples, the buffers taking turns
+  int cur = 0;                // the buffer holding them
+  int valid = 0;              // how many exist since the last reset
+  uint64_t counter = 0;       // wide-sample index of the next call's first sample
+  // fmx_wb_set_freq's staging image (pinned): one channel's rows and its f mod
+  // Fs; ev marks the last copy out of it
+  uint16_t *stage = nullptr;
+  hipEvent_t ev = nullptr;
+  bool ev_set = false;
+};
+Wb *W(void *p) { return static_cast<Wb *>(p); }
+size_t wb_sample_bytes(const WbPlan &p) { return p.format == FMX_WB_S16 ? 4 : 2; }
+void wb_free(Wb *w) {
+  if (w->d_w) hipFree(w->d_w);
+  if (w->d_fpos) hipFree(w->d_fpos);
+  for (void *b : w->d_hist)
+    if (b) hipFree(b);
+  if (w->stage) hipHostFree(w->stage);
+  if (w->ev) hipEventDestroy(w->ev);
+  delete w;
+}
+} // namespace
+
+int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, int n_channels, void **wb) {
+  Handle *h = H(handle);
+  if (wb) *wb = nullptr;
+  if (!h) return FMX_E_INVALID;
+  if (!cfg || !freq_hz || !wb || n_channels < 1) {
+    h->err = "fmx_wb_create: null argument or no channels";
+    return FMX_E_INVALID;
+  }
+  WbPlan p;
+  int rc = wb_plan(*cfg, &p, &h->err);
+  if (rc != FMX_OK) return rc;
+  for (int c = 0; c < n_channels; ++c)
+    if (!wb_freq_ok(p, freq_hz[c])) {
+      h->err = "fmx_wb_create: channel " + std::to_string(c) + " lies outside +- wide_rate / 2";
+      return FMX_E_INVALID;
+    }
+  HIP_TRY(hipSetDevice(h->device));
+  Wb *w = new (std::nothrow) Wb();
+  if (!w) return FMX_E_NOMEM;
+  w->h = h;
+  w->p = p;
+  w->C = n_channels;
+  const size_t row = static_cast<size_t>(4) * p.Lp, hist_bytes = static_cast<size_t>(p.L - 1) * wb_sample_bytes(p);
+  std::vector<uint16_t> rows(row * n_channels);
+  std::vector<uint32_t> fpos(n_channels);
+  for (int c = 0; c < n_channels; ++c) {
+    wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
+    fpos[c] = wb_freq_mod(p, freq_hz[c]);
+  }
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->d_w), rows.size() * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_fpos), fpos.size() * sizeof(uint32_t));
+  for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&w->d_hist[b], hist_bytes);
+  if (e != hipSuccess) {
+    h->err = std::string("fmx_wb_create: hipMalloc failed: ") + hipGetErrorString(e);
+    wb_free(w);
+    return FMX_E_NOMEM;
+  }
+  e = hipHostMalloc(reinterpret_cast<void **>(&w->stage), row * sizeof(uint16_t) + sizeof(uint32_t), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev, hipEventDisableTiming);
+  // synchronous copies: the tables are complete before the first call is queued
+  if (e == hipSuccess) e = hipMemcpy(w->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(w->d_fpos, fpos.data(), fpos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    h->err = std::string("fmx_wb_create: ") + hipGetErrorString(e);
+    wb_free(w);
+    return FMX_E_HIP;
+  }
+  *wb = w;
+  return FMX_OK;
+}
+
+int fmx_wb_destroy(void *wb) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  if (w->h->sA) hipStreamSynchronize(w->h->sA);
+  wb_free(w);
+  return FMX_OK;
+}
+
+int fmx_wb_set_freq(void *wb, int channel, int freq_hz) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  Handle *h = w->h;
+  if (channel < 0 || channel >= w->C || !wb_freq_ok(w->p, freq_hz)) {
+    h->err = "fmx_wb_set_freq: channel or frequency out of range";
+    return FMX_E_INVALID;
+  }
+  if (w->ev_set) HIP_TRY(hipEventSynchronize(w->ev)); // the staging image's last copy has left it
+  const size_t row = static_cast<size_t>(4) * w->p.Lp;
+  wb_weight_rows(w->p, freq_hz, w->stage);
+  const uint32_t fm = wb_freq_mod(w->p, freq_hz);
+  std::memcpy(w->stage + row, &fm, sizeof(fm));
+  // on the stage stream: after the calls queued so far, before later ones
+  HIP_TRY(hipMemcpyAsync(w->d_w + row * channel, w->stage, row * sizeof(uint16_t), hipMemcpyHostToDevice, h->sA));
+  HIP_TRY(hipMemcpyAsync(w->d_fpos + channel, w->stage + row, sizeof(uint32_t), hipMemcpyHostToDevice, h->sA));
+  HIP_TRY(hipEventRecord(w->ev, h->sA));
+  w->ev_set = true;
+  return FMX_OK;
+}
+
+int fmx_wb_reset(void *wb, int64_t sample0) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  if (sample0 < 0) {
+    w->h->err = "fmx_wb_reset: negative sample index";
+    return FMX_E_INVALID;
+  }
+  w->valid = 0; // the kernel reads zeros for samples before the stream's start
+  w->counter = static_cast<uint64_t>(sample0);
+  return FMX_OK;
+}
+
+int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int out_stride) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  Handle *h = w->h;
+  const WbPlan &p = w->p;
+  if (n_out < 0 || (n_out > 0 && (!d_wide || !d_out || out_stride < n_out))) {
+    h->err = "fmx_wb_process: null buffer, negative n_out or out_stride < n_out";
+    return FMX_E_INVALID;
+  }
+  if (n_out > p.block) {
+    h->err = "fmx_wb_process: n_out exceeds the object's block";
+    return FMX_E_CAPACITY;
+  }
+  if (n_out == 0) return FMX_OK;
+  int rc;
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  WbArgs a{};
+  a.in = d_wide;
+  a.s16 = p.format == FMX_WB_S16;
+  a.D = p.D;
+  a.L = p.L;
+  a.Lp = p.Lp;
+  a.n_out = n_out;
+  a.C = w->C;
+  a.w = w->d_w;
+  a.fpos = w->d_fpos;
+  a.hist = w->d_hist[w->cur];
+  a.hist_out = w->d_hist[w->cur ^ 1];
+  a.valid = w->valid;
+  a.fs = static_cast<uint32_t>(p.fs);
+  a.base_mod = static_cast<uint32_t>(w->counter % static_cast<uint64_t>(p.fs));
+  a.inv_fs = 1.0 / static_cast<double>(p.fs);
+  a.scale = static_cast<float>(std::ldexp(a.s16 ? 1.0 / 32768.0 : 1.0 / 255.0, -p.sexp));
+  a.out = d_out;
+  a.out_stride = out_stride;
+  if ((rc = launch_wb(a, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_process: kernel launch failed";
+    return rc;
+  }
+  const int64_t n_in = static_cast<int64_t>(n_out) * p.D;
+  w->cur ^= 1;
+  w->valid = static_cast<int>(std::min<int64_t>(p.L - 1, w->valid + n_in));
+  w->counter += static_cast<uint64_t>(n_in);
+  return FMX_OK;
+}
+
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes) {
   Handle *h = H(handle);
   if (!h || !d_ptr) return FMX_E_INVALID;

@@ -281,6 +281,45 @@ struct ResetList {
 };
 int launch_reset(const ResetArgs &a, void *stream);
 int launch_reset_list(const ResetArgs &a, const ResetList &L, int parts, int st_buf, void *stream);
+// ---- wideband channelizer (fmx_wb_design.cpp, fmx_wb.inc) ----
+// Geometry and taps of one fmx_wb_config; the f16 weight rows are built per
+// channel frequency from it.
+struct WbPlan {
+  int D = 0, tpp = 0, L = 0, Lp = 0; // Lp: L rounded up to the MFMA's K = 32
+  int fs = 0, format = 0, block = 0; // wide rate, FMX_WB_*, outputs per call at most
+  int sexp = 0;                      // weights enter the tables as W * 2^sexp
+  float fc = 0.0f;
+  std::vector<double> g;             // 2 fc h[k], k = 0..L-1
+};
+int wb_plan(const fmx_wb_config &cfg, WbPlan *p, std::string *err);
+bool wb_freq_ok(const WbPlan &p, int freq_hz);
+// one channel's rows [4][Lp] (re hi, re lo, im hi, im lo): entry kk holds tap
+// k = Lp - 1 - kk (zero for k >= L) as f16 bits
+void wb_weight_rows(const WbPlan &p, int freq_hz, uint16_t *rows);
+// W[k] (re, im) read back from such rows
+void wb_rows_to_taps(const WbPlan &p, const uint16_t *rows, float *out);
+uint32_t wb_freq_mod(const WbPlan &p, int freq_hz); // f mod Fs in [0, Fs)
+
+struct WbArgs {
+  const void *in;       // n_out * D wide samples, interleaved I/Q
+  int s16;              // int16 pairs, else u8 pairs
+  int in_al;            // a whole sample (2 or 4 bytes) may be loaded at once
+  int D, L, Lp, n_out, C;
+  const uint16_t *w;    // [C][4][Lp] weight rows
+  const uint32_t *fpos; // [C] f mod Fs
+  const void *hist;     // the last L - 1 raw samples before this call
+  void *hist_out;       // the same after it (another buffer)
+  int valid;            // samples of hist that exist (since the last reset)
+  uint32_t fs;          // wide rate
+  uint32_t base_mod;    // the call's first sample index mod Fs
+  double inv_fs;
+  float scale;          // accumulator -> output
+  float *out;
+  int out_stride;
+  int nt;               // 16-output tiles per workgroup (set by the launcher)
+};
+int launch_wb(const WbArgs &a, void *stream);
+
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps
 

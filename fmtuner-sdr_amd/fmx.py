@@ -63,6 +63,13 @@ class SynthConfig(C.Structure):
                 ("n_bits", C.c_int), ("level_spread_db", C.c_float)]
 
 
+FMX_WB_U8, FMX_WB_S16 = 0, 1
+
+
+class WbConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("wide_rate", "dsp_rate", "format", "taps_per_phase", "block")]
+
+
 _lib = None
 _OPTIONAL = {"fmx_build_info", "fmx_host_stats", "fmx_diag_set", "fmx_diag_rds_ring"}  # absent from older libraries (A/B against past revisions)
 
@@ -97,6 +104,12 @@ def lib():
         "fmx_stereo": (i, [vp, vp, i, i, vp, vp, i, vp, vp]),
         "fmx_afpost": (i, [vp, vp, vp, i, i, vp, vp, i, i, vp]),
         "fmx_rds": (i, [vp, vp, i, i, vp, i, vp]),
+        "fmx_wb_create": (i, [vp, C.POINTER(WbConfig), C.POINTER(i), i, C.POINTER(vp)]),
+        "fmx_wb_destroy": (i, [vp]),
+        "fmx_wb_set_freq": (i, [vp, i, i]),
+        "fmx_wb_reset": (i, [vp, C.c_int64]),
+        "fmx_wb_process": (i, [vp, vp, i, vp, i]),
+        "fmx_wb_weights": (i, [C.POINTER(WbConfig), i, fp, i]),
         "fmx_malloc": (i, [vp, C.POINTER(vp), sz]),
         "fmx_free": (i, [vp, vp]),
         "fmx_memcpy_h2d": (i, [vp, vp, vp, sz]),
@@ -278,6 +291,65 @@ class Handle:
         v = (C.c_double * 3)()
         self._ck(self.L.fmx_host_stats(self.h, v, 3), "fmx_host_stats")
         return {"image_waits": int(v[0]), "blocked": int(v[1]), "blocked_ms": round(v[2], 4)}
+
+
+def make_wb_config(wide_rate=2_400_000, dsp_rate=240_000, format=FMX_WB_S16, taps_per_phase=0, block=4096):
+    return WbConfig(wide_rate, dsp_rate, format, taps_per_phase, block)
+
+
+class Wideband:
+    """The wideband channelizer of one Handle (fmx_wb_*): one wide IQ capture
+    in, the complex baseband rows of len(freq_hz) tuned channels out --
+    Handle.demod's input.  Close it before its handle."""
+
+    def __init__(self, handle, wcfg, freq_hz):
+        self.L = lib()
+        self.handle = handle
+        self.cfg = wcfg
+        self.n = len(freq_hz)
+        f = (C.c_int * self.n)(*[int(v) for v in freq_hz])
+        w = C.c_void_p()
+        rc = self.L.fmx_wb_create(handle.h, C.byref(wcfg), f, self.n, C.byref(w))
+        self.w = w if rc == FMX_OK else None
+        if rc != FMX_OK:
+            raise FmxError(f"fmx_wb_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+
+    def _ck(self, rc, what):
+        if rc != FMX_OK:
+            raise FmxError(f"{what} failed ({rc}): {self.L.fmx_last_error(self.handle.h).decode()}")
+
+    def close(self):
+        if self.w is not None and self.handle.h is not None:
+            self.L.fmx_wb_destroy(self.w)
+        self.w = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_freq(self, channel, freq_hz):
+        self._ck(self.L.fmx_wb_set_freq(self.w, channel, int(freq_hz)), "fmx_wb_set_freq")
+
+    def reset(self, sample0=0):
+        self._ck(self.L.fmx_wb_reset(self.w, sample0), "fmx_wb_reset")
+
+    def process(self, d_wide, n_out, d_out, out_stride):
+        """d_wide: n_out * D interleaved I/Q samples; d_out: [n][out_stride] complex float."""
+        self._ck(self.L.fmx_wb_process(self.w, C.c_void_p(d_wide), n_out, C.c_void_p(d_out), out_stride),
+                 "fmx_wb_process")
+
+
+def wb_weights(wcfg, freq_hz):
+    """fmx_wb_weights: W[k] as complex64 [L], read back from the f16 tables."""
+    import numpy as np
+    n = lib().fmx_wb_weights(C.byref(wcfg), int(freq_hz), None, 0)
+    if n < 0:
+        raise FmxError(f"fmx_wb_weights failed ({n})")
+    buf = np.zeros(n, dtype=np.float32)
+    lib().fmx_wb_weights(C.byref(wcfg), int(freq_hz), buf.ctypes.data_as(C.POINTER(C.c_float)), n)
+    return buf.view(np.complex64)
 
 
 def synth_rds_bits(scfg, ch0, n_ch):

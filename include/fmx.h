@@ -47,11 +47,12 @@
 extern "C" {
 #endif
 
-/* ABI history: 9 (round 6) adds fmx_diag_set / fmx_diag_rds_ring and fmx_build_info; 8 (round 5) adds FMX_K_BITS (FMX_K_COUNT 8); 7 (round 5) adds fmx_host_stats and FMX_K_FRONTEND_GENERIC (FMX_K_COUNT 7); 6 (round 4) adds FMX_K_PILOT (FMX_K_COUNT 6); 5 (round 4) added FMX_K_RS (FMX_K_COUNT 5; fmx_kernel_times
+/* ABI history: 10 adds the wideband channelizer (fmx_wb_*: one wide IQ capture in, every tuned
+ * channel's baseband out); 9 (round 6) adds fmx_diag_set / fmx_diag_rds_ring and fmx_build_info; 8 (round 5) adds FMX_K_BITS (FMX_K_COUNT 8); 7 (round 5) adds fmx_host_stats and FMX_K_FRONTEND_GENERIC (FMX_K_COUNT 7); 6 (round 4) adds FMX_K_PILOT (FMX_K_COUNT 6); 5 (round 4) added FMX_K_RS (FMX_K_COUNT 5; fmx_kernel_times
  * fills at most n entries); 4 (round 3) added fmx_synth_config.level_spread_db,
  * which changed that struct's size: callers must be rebuilt against this
  * header. */
-#define FMX_ABI_VERSION 9
+#define FMX_ABI_VERSION 10
 
 enum {
   FMX_OK = 0,
@@ -212,6 +213,48 @@ int fmx_afpost(void *handle, const float *d_left, const float *d_right, int in_s
 /* RDSDecoder::process: groups of this call per channel */
 int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_group *d_groups,
             int groups_stride, int *d_group_count);
+
+/* ---- wideband channelizer: one wide IQ capture in, every channel's baseband out ----
+ * The reference's ComplexDecimator generalised to tuned channels.  With
+ * D = wide_rate / dsp_rate, L = D * taps_per_phase taps h = firdes_kaiser(L,
+ * fc, 80 dB), fc = min(0.45 / D, 0.45), channel c tuned to freq_hz[c]
+ * (relative to the capture's centre, |f| <= wide_rate / 2) produces
+ *   y_c[n] = 2 fc sum_k h[k] x[nD - k] exp(-j 2 pi f_c (nD - k) / wide_rate)
+ * with x[i < 0] = 0, i the wide-sample index since the last reset plus its
+ * sample0, x = (b - 127.5) / 127.5 for FMX_WB_U8 (interleaved u8 I/Q) and
+ * v / 32768 for FMX_WB_S16 (interleaved int16 I/Q).  At f = 0 this is
+ * ComplexDecimator::executeComplex.  d_out is [n_channels][out_stride] complex
+ * float at dsp_rate: fmx_demod's input on a handle of n_channels channels.
+ * The object keeps the last L - 1 raw wide samples and a 64-bit sample
+ * counter; its outputs do not depend on how the stream is cut into calls.
+ * Calls are queued on the handle's stream (a following fmx_demod is ordered
+ * behind them); the object is destroyed before its handle.  Geometry: d_wide
+ * needs its element's alignment only (1 byte for u8, 2 for int16), d_out 4
+ * bytes; out_stride counts complex elements and is >= n_out (fmx_demod's
+ * in_stride counts floats: 2 * out_stride); cells past n_out are never
+ * written. */
+enum { FMX_WB_U8 = 0, FMX_WB_S16 = 1 };
+typedef struct {
+  int wide_rate;      /* integer multiple D of dsp_rate, 2 <= D <= 128             */
+  int dsp_rate;
+  int format;         /* FMX_WB_*                                                  */
+  int taps_per_phase; /* 4..28; 0: the reference's rule (28 from D = 8, 20 from 4, else 12) */
+  int block;          /* max outputs per channel and call                          */
+} fmx_wb_config;
+int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, int n_channels, void **wb);
+int fmx_wb_destroy(void *wb);
+/* ordered after the calls queued so far and before later ones; from the next
+ * call on the channel's outputs are those of a channel that had always been
+ * at freq_hz (the history is raw input) */
+int fmx_wb_set_freq(void *wb, int channel, int freq_hz);
+/* clears the history; the next call's first wide sample has index sample0 */
+int fmx_wb_reset(void *wb, int64_t sample0);
+/* consumes n_out * D wide samples (n_out <= block, else FMX_E_CAPACITY) */
+int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int out_stride);
+/* host only: the channel weights W[k] = 2 fc h[k] exp(+j 2 pi f k / wide_rate),
+ * k = 0..L-1, as 2L floats (re, im) read back from the kernel's f16 hi + lo
+ * tables.  Returns 2L (negative on error). */
+int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap);
 
 /* ---- device memory helpers (so C/FFI callers need no HIP headers) ---- */
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes);

@@ -2066,6 +2066,150 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
   return FMX_OK;
 }
 
+/* ---- band scan (fmx.h; kernels in fmx_wb_scan.inc) ---- */
+namespace {
+struct WbScan {
+  Handle *h = nullptr;
+  WbPlan p;
+  int P = 0;                  // scan points
+  uint16_t *d_w = nullptr;    // [P][4][Lp] weight rows
+  float *d_partial = nullptr; // [(P + 15) / 16][workgroups of a full block][16]
+  uint32_t *d_clip = nullptr; // [clip workgroups of a full block][2]
+  float *d_sm = nullptr;      // [P][2] level smoothers
+  double sp[4] = {0.0, -4.0, -55.0, -19.0}; // gain*factor, bias, floor, ceil
+};
+WbScan *WS(void *p) { return static_cast<WbScan *>(p); }
+void wb_scan_free(WbScan *s) {
+  if (s->d_w) hipFree(s->d_w);
+  if (s->d_partial) hipFree(s->d_partial);
+  if (s->d_clip) hipFree(s->d_clip);
+  if (s->d_sm) hipFree(s->d_sm);
+  delete s;
+}
+} // namespace
+
+int fmx_wb_scan_create(void *handle, const fmx_wb_scan_config *cfg, void **scan) {
+  Handle *h = H(handle);
+  if (scan) *scan = nullptr;
+  if (!h) return FMX_E_INVALID;
+  if (!cfg || !scan) {
+    h->err = "fmx_wb_scan_create: null argument";
+    return FMX_E_INVALID;
+  }
+  WbPlan p;
+  int rc = wb_scan_plan(*cfg, &p, &h->err);
+  if (rc != FMX_OK) return rc;
+  const int s16 = p.format == FMX_WB_S16;
+  const int nt = wb_scan_tiles(p.D, p.Lp, s16);
+  if (nt < 1 || p.block <= p.tpp) {
+    h->err = "fmx_wb_scan_create: block must exceed taps_per_phase";
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  WbScan *s = new (std::nothrow) WbScan();
+  if (!s) return FMX_E_NOMEM;
+  s->h = h;
+  s->p = p;
+  s->P = cfg->n_points;
+  const size_t row = static_cast<size_t>(4) * p.Lp;
+  std::vector<uint16_t> rows(row * s->P);
+  for (int k = 0; k < s->P; ++k) wb_weight_rows(p, cfg->start_hz + k * cfg->step_hz, rows.data() + row * k);
+  const size_t n_partial = static_cast<size_t>((s->P + 15) / 16) * wb_scan_workgroups(p.block, p.tpp, nt) * 16;
+  const size_t n_clip = static_cast<size_t>(wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D)) * 2;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->d_w), rows.size() * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_partial), n_partial * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_clip), n_clip * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_sm), static_cast<size_t>(s->P) * 2 * sizeof(float));
+  if (e != hipSuccess) {
+    h->err = std::string("fmx_wb_scan_create: hipMalloc failed: ") + hipGetErrorString(e);
+    wb_scan_free(s);
+    return FMX_E_NOMEM;
+  }
+  // synchronous: the tables are complete before the first call is queued
+  e = hipMemcpy(s->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(s->d_sm, 0, static_cast<size_t>(s->P) * 2 * sizeof(float));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    h->err = std::string("fmx_wb_scan_create: ") + hipGetErrorString(e);
+    wb_scan_free(s);
+    return FMX_E_HIP;
+  }
+  *scan = s;
+  return FMX_OK;
+}
+
+int fmx_wb_scan_destroy(void *scan) {
+  WbScan *s = WS(scan);
+  if (!s) return FMX_E_INVALID;
+  if (s->h->sA) hipStreamSynchronize(s->h->sA);
+  wb_scan_free(s);
+  return FMX_OK;
+}
+
+int fmx_wb_scan_set_signal_params(void *scan, int applied_gain_db, double gain_comp_factor, double bias_db,
+                                  double floor_dbfs, double ceil_dbfs) {
+  WbScan *s = WS(scan);
+  if (!s) return FMX_E_INVALID;
+  // computeSignalLevel: compensated = (dbfs - gain * factor) + bias; the values travel with each launch
+  s->sp[0] = static_cast<double>(applied_gain_db) * gain_comp_factor;
+  s->sp[1] = bias_db;
+  s->sp[2] = floor_dbfs;
+  s->sp[3] = ceil_dbfs;
+  return FMX_OK;
+}
+
+int fmx_wb_scan_reset(void *scan) {
+  WbScan *s = WS(scan);
+  if (!s) return FMX_E_INVALID;
+  Handle *h = s->h;
+  int rc;
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  HIP_TRY(hipMemsetAsync(s->d_sm, 0, static_cast<size_t>(s->P) * 2 * sizeof(float), h->sA));
+  return FMX_OK;
+}
+
+int fmx_wb_scan_process(void *scan, const void *d_wide, int n_out, fmx_signal_level *d_level) {
+  WbScan *s = WS(scan);
+  if (!s) return FMX_E_INVALID;
+  Handle *h = s->h;
+  const WbPlan &p = s->p;
+  if (!d_wide || !d_level) {
+    h->err = "fmx_wb_scan_process: null buffer";
+    return FMX_E_INVALID;
+  }
+  if (n_out <= p.tpp) {
+    h->err = "fmx_wb_scan_process: n_out must exceed taps_per_phase (the outputs before it are left out)";
+    return FMX_E_INVALID;
+  }
+  if (n_out > p.block) {
+    h->err = "fmx_wb_scan_process: n_out exceeds the object's block";
+    return FMX_E_CAPACITY;
+  }
+  int rc;
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  WbScanArgs a{};
+  a.in = d_wide;
+  a.s16 = p.format == FMX_WB_S16;
+  a.D = p.D;
+  a.tpp = p.tpp;
+  a.Lp = p.Lp;
+  a.n_out = n_out;
+  a.P = s->P;
+  a.w = s->d_w;
+  a.partial = s->d_partial;
+  a.clip = s->d_clip;
+  a.sm = s->d_sm;
+  a.level = d_level;
+  // raw integers (2 b - 255 for u8) times weights * 2^sexp, squared
+  a.pscale = std::ldexp(a.s16 ? std::ldexp(1.0, -30) : 1.0 / (255.0 * 255.0), -2 * p.sexp);
+  for (int k = 0; k < 4; ++k) a.sp[k] = s->sp[k];
+  if ((rc = launch_wb_scan(a, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_scan_process: kernel launch failed";
+    return rc;
+  }
+  return FMX_OK;
+}
+
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes) {
   Handle *h = H(handle);
   if (!h || !d_ptr) return FMX_E_INVALID;

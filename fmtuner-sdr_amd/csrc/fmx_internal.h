@@ -299,6 +299,8 @@ void wb_weight_rows(const WbPlan &p, int freq_hz, uint16_t *rows);
 // W[k] (re, im) read back from such rows
 void wb_rows_to_taps(const WbPlan &p, const uint16_t *rows, float *out);
 uint32_t wb_freq_mod(const WbPlan &p, int freq_hz); // f mod Fs in [0, Fs)
+// wb_plan of cfg.wb plus the scan's conditions on its points
+int wb_scan_plan(const fmx_wb_scan_config &cfg, WbPlan *p, std::string *err);
 
 struct WbArgs {
   const void *in;       // n_out * D wide samples, interleaved I/Q
@@ -319,6 +321,25 @@ struct WbArgs {
   int nt;               // 16-output tiles per workgroup (set by the launcher)
 };
 int launch_wb(const WbArgs &a, void *stream);
+
+// ---- band scan (fmx_wb_scan.inc; plan and weight rows are the channelizer's) ----
+struct WbScanArgs {
+  const void *in;          // n_out * D wide samples, interleaved I/Q
+  int s16, in_al;          // as WbArgs
+  int D, tpp, Lp, n_out, P; // P scan points
+  const uint16_t *w;       // [P][4][Lp] weight rows
+  float *partial;          // [(P + 15) / 16][nwg][16] sums of |raw y|^2
+  uint32_t *clip;          // [nclip][2] hard- and near-clipped samples
+  float *sm;               // [P][2] smoother value, initialised flag
+  fmx_signal_level *level; // [P]
+  double pscale;           // raw |y|^2 -> |y|^2
+  double sp[4];            // gain*factor, bias, floor, ceil
+  int nt, nwg, nclip;      // tiles per workgroup, workgroups per point group, clip workgroups (set by the launcher)
+};
+int wb_scan_tiles(int D, int Lp, int s16);
+int wb_scan_workgroups(int n_out, int tpp, int nt);
+int wb_scan_clip_workgroups(long n_in);
+int launch_wb_scan(const WbScanArgs &a, void *stream);
 
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps

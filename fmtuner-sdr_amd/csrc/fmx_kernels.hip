@@ -3887,4 +3887,5 @@ int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sa
   return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
 }
 #include "fmx_wb.inc"
+#include "fmx_wb_scan.inc"
 } // namespace fmx

@@ -116,7 +116,45 @@ void wb_rows_to_taps(const WbPlan &p, const uint16_t *rows, float *out) {
   }
 }
 
+int wb_scan_plan(const fmx_wb_scan_config &cfg, WbPlan *p, std::string *err) {
+  auto fail = [&](const char *m) {
+    if (err) *err = m;
+    return FMX_E_INVALID;
+  };
+  const int rc = wb_plan(cfg.wb, p, err);
+  if (rc != FMX_OK) return rc;
+  if (cfg.step_hz < 1) return fail("fmx_wb_scan: step_hz must be at least 1");
+  if (cfg.n_points < 1 || cfg.n_points > 8192) return fail("fmx_wb_scan: n_points must be 1..8192");
+  const int64_t last = static_cast<int64_t>(cfg.start_hz) + static_cast<int64_t>(cfg.n_points - 1) * cfg.step_hz;
+  if (2 * static_cast<int64_t>(cfg.start_hz) < -static_cast<int64_t>(p->fs) || 2 * last > p->fs)
+    return fail("fmx_wb_scan: a point lies outside +- wide_rate / 2");
+  return FMX_OK;
+}
+
 } // namespace fmx
+
+extern "C" int fmx_wb_scan_points(const fmx_wb_scan_config *cfg, int *freq_hz, int cap) {
+  if (!cfg) return FMX_E_INVALID;
+  fmx::WbPlan p;
+  const int rc = fmx::wb_scan_plan(*cfg, &p, nullptr);
+  if (rc != FMX_OK) return rc;
+  for (int k = 0; freq_hz && k < cfg->n_points && k < cap; ++k) freq_hz[k] = cfg->start_hz + k * cfg->step_hz;
+  return cfg->n_points;
+}
+
+extern "C" int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int min_spacing, int *idx, int cap) {
+  if (n < 0 || min_spacing < 0 || (n > 0 && !dbfs)) return FMX_E_INVALID;
+  int count = 0;
+  for (int p = 0; p < n; ++p) {
+    bool peak = dbfs[p] >= min_dbfs;
+    for (int q = std::max(0, p - min_spacing); peak && q < p; ++q) peak = dbfs[p] > dbfs[q];
+    for (int q = p + 1; peak && q < n && q - p <= min_spacing; ++q) peak = dbfs[p] >= dbfs[q];
+    if (!peak) continue;
+    if (idx && count < cap) idx[count] = p;
+    ++count;
+  }
+  return count;
+}
 
 extern "C" int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap) {
   if (!cfg) return FMX_E_INVALID;

@@ -70,6 +70,10 @@ class WbConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("wide_rate", "dsp_rate", "format", "taps_per_phase", "block")]
 
 
+class WbScanConfig(C.Structure):
+    _fields_ = [("wb", WbConfig), ("start_hz", C.c_int), ("step_hz", C.c_int), ("n_points", C.c_int)]
+
+
 _lib = None
 _OPTIONAL = {"fmx_build_info", "fmx_host_stats", "fmx_diag_set", "fmx_diag_rds_ring"}  # absent from older libraries (A/B against past revisions)
 
@@ -110,6 +114,13 @@ def lib():
         "fmx_wb_reset": (i, [vp, C.c_int64]),
         "fmx_wb_process": (i, [vp, vp, i, vp, i]),
         "fmx_wb_weights": (i, [C.POINTER(WbConfig), i, fp, i]),
+        "fmx_wb_scan_create": (i, [vp, C.POINTER(WbScanConfig), C.POINTER(vp)]),
+        "fmx_wb_scan_destroy": (i, [vp]),
+        "fmx_wb_scan_set_signal_params": (i, [vp, i, C.c_double, C.c_double, C.c_double, C.c_double]),
+        "fmx_wb_scan_reset": (i, [vp]),
+        "fmx_wb_scan_process": (i, [vp, vp, i, vp]),
+        "fmx_wb_scan_points": (i, [C.POINTER(WbScanConfig), C.POINTER(i), i]),
+        "fmx_scan_peaks": (i, [C.POINTER(C.c_double), i, C.c_double, i, C.POINTER(i), i]),
         "fmx_malloc": (i, [vp, C.POINTER(vp), sz]),
         "fmx_free": (i, [vp, vp]),
         "fmx_memcpy_h2d": (i, [vp, vp, vp, sz]),
@@ -350,6 +361,77 @@ def wb_weights(wcfg, freq_hz):
     buf = np.zeros(n, dtype=np.float32)
     lib().fmx_wb_weights(C.byref(wcfg), int(freq_hz), buf.ctypes.data_as(C.POINTER(C.c_float)), n)
     return buf.view(np.complex64)
+
+
+def make_wb_scan_config(wide_rate=2_400_000, dsp_rate=240_000, format=FMX_WB_S16, taps_per_phase=0, block=4096,
+                        start_hz=-1_100_000, step_hz=100_000, n_points=23):
+    return WbScanConfig(WbConfig(wide_rate, dsp_rate, format, taps_per_phase, block), start_hz, step_hz, n_points)
+
+
+class WidebandScan:
+    """The band scan of one Handle (fmx_wb_scan_*): one wide IQ capture in,
+    one fmx_signal_level record per scan point out.  Close it before its handle."""
+
+    def __init__(self, handle, scfg):
+        self.L = lib()
+        self.handle = handle
+        self.cfg = scfg
+        self.n = scfg.n_points
+        s = C.c_void_p()
+        rc = self.L.fmx_wb_scan_create(handle.h, C.byref(scfg), C.byref(s))
+        self.s = s if rc == FMX_OK else None
+        if rc != FMX_OK:
+            raise FmxError(f"fmx_wb_scan_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+
+    def _ck(self, rc, what):
+        if rc != FMX_OK:
+            raise FmxError(f"{what} failed ({rc}): {self.L.fmx_last_error(self.handle.h).decode()}")
+
+    def close(self):
+        if self.s is not None and self.handle.h is not None:
+            self.L.fmx_wb_scan_destroy(self.s)
+        self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_signal_params(self, applied_gain_db=0, gain_comp_factor=0.5, bias_db=-4.0, floor_dbfs=-55.0,
+                          ceil_dbfs=-19.0):
+        self._ck(self.L.fmx_wb_scan_set_signal_params(self.s, applied_gain_db, gain_comp_factor, bias_db, floor_dbfs,
+                                                      ceil_dbfs), "fmx_wb_scan_set_signal_params")
+
+    def reset(self):
+        self._ck(self.L.fmx_wb_scan_reset(self.s), "fmx_wb_scan_reset")
+
+    def process(self, d_wide, n_out, d_level):
+        """d_wide: n_out * D interleaved I/Q samples; d_level: [n_points] fmx_signal_level (40 bytes each)."""
+        self._ck(self.L.fmx_wb_scan_process(self.s, C.c_void_p(d_wide), n_out, C.c_void_p(d_level)),
+                 "fmx_wb_scan_process")
+
+
+def wb_scan_points(scfg):
+    """fmx_wb_scan_points: the plan's point frequencies (Hz from the capture's centre)."""
+    n = lib().fmx_wb_scan_points(C.byref(scfg), None, 0)
+    if n < 0:
+        raise FmxError(f"fmx_wb_scan_points failed ({n})")
+    f = (C.c_int * n)()
+    lib().fmx_wb_scan_points(C.byref(scfg), f, n)
+    return list(f)
+
+
+def scan_peaks(dbfs, min_dbfs, min_spacing):
+    """fmx_scan_peaks: ascending indices of the local maxima of dbfs at or above min_dbfs."""
+    v = [float(x) for x in dbfs]
+    n = len(v)
+    arr = (C.c_double * max(n, 1))(*v)
+    idx = (C.c_int * max(n, 1))()
+    k = lib().fmx_scan_peaks(arr, n, float(min_dbfs), int(min_spacing), idx, n)
+    if k < 0:
+        raise FmxError(f"fmx_scan_peaks failed ({k})")
+    return list(idx[:k])
 
 
 def synth_rds_bits(scfg, ch0, n_ch):

@@ -47,12 +47,13 @@
 extern "C" {
 #endif
 
-/* ABI history: 10 adds the wideband channelizer (fmx_wb_*: one wide IQ capture in, every tuned
+/* ABI history: 11 adds the band scan (fmx_wb_scan_*, fmx_scan_peaks: one wide IQ capture in, the RF
+ * level of every scan point out); 10 adds the wideband channelizer (fmx_wb_*: one wide IQ capture in, every tuned
  * channel's baseband out); 9 (round 6) adds fmx_diag_set / fmx_diag_rds_ring and fmx_build_info; 8 (round 5) adds FMX_K_BITS (FMX_K_COUNT 8); 7 (round 5) adds fmx_host_stats and FMX_K_FRONTEND_GENERIC (FMX_K_COUNT 7); 6 (round 4) adds FMX_K_PILOT (FMX_K_COUNT 6); 5 (round 4) added FMX_K_RS (FMX_K_COUNT 5; fmx_kernel_times
  * fills at most n entries); 4 (round 3) added fmx_synth_config.level_spread_db,
  * which changed that struct's size: callers must be rebuilt against this
  * header. */
-#define FMX_ABI_VERSION 10
+#define FMX_ABI_VERSION 11
 
 enum {
   FMX_OK = 0,
@@ -255,6 +256,54 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
  * k = 0..L-1, as 2L floats (re, im) read back from the kernel's f16 hi + lo
  * tables.  Returns 2L (negative on error). */
 int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap);
+
+/* ---- band scan: the RF level of every scan point from one wide capture ----
+ * The reference's scan (main.cpp:1064-1121: retune, three reads,
+ * computeSignalLevel of each) on a shared capture.  Point p lies at
+ * start_hz + p * step_hz from the capture's centre; wb.dsp_rate is the
+ * points' measurement rate (D = wide_rate / dsp_rate, pass band +-0.45
+ * dsp_rate) and need not be the handle's.  One call is one read of every
+ * point: it consumes n_out * D wide samples and keeps nothing of the signal
+ * (the stream may have gaps between reads, as after the reference's retune).
+ * With y_p[n] the channelizer's output above for a channel at point p, x
+ * indexed from the call's first sample, tpp = L / D:
+ *   P_p  = 1 / (n_out - tpp) sum_{n = tpp}^{n_out - 1} |y_p[n]|^2
+ *   rms  = sqrt(max(1e-15, 0.5 P_p)),  dbfs = 20 log10(rms + 1e-12)
+ * and compensated_dbfs, level120, level120_smoothed (one smoother per point)
+ * as computeSignalLevel / smoothSignalLevel (signal_level.cpp:187-214).  The
+ * outputs n < tpp, whose windows reach before the call, are left out: no
+ * sample before the call's first is needed.  0.5 P is the reference's
+ * 0.5 (varI + varQ) WITHOUT its mean removal: the reference removes the mean
+ * of one tuned read, which a shared capture has no counterpart of, so a
+ * capture's DC offset shows at the points within the pass band of the centre
+ * (as in fmx_wb_process's rows).  hard_clip_ratio and near_clip_ratio are
+ * those of the call's n_out * D raw samples (clipped samples / samples; u8 by
+ * the reference's byte thresholds, signal_level.cpp:172-177, an int16 by its
+ * top byte b = (v >> 8) + 128), the same in every record.  n_out <= tpp is
+ * FMX_E_INVALID, n_out > block FMX_E_CAPACITY.  Calls are queued on the
+ * handle's stream; the object is destroyed before its handle.  Geometry:
+ * d_wide needs its element's alignment only, d_level 8 bytes; cells outside
+ * [0, n_points) are never written.  The signal parameters default to
+ * fmx_set_signal_params' (gain 0, factor 0.5, bias -4, floor -55, ceil -19). */
+typedef struct {
+  fmx_wb_config wb;
+  int start_hz, step_hz, n_points; /* step_hz >= 1, 1 <= n_points <= 8192, every point within +- wide_rate / 2 */
+} fmx_wb_scan_config;
+int fmx_wb_scan_create(void *handle, const fmx_wb_scan_config *cfg, void **scan);
+int fmx_wb_scan_destroy(void *scan);
+int fmx_wb_scan_set_signal_params(void *scan, int applied_gain_db, double gain_comp_factor, double bias_db,
+                                  double floor_dbfs, double ceil_dbfs);
+/* clears the per-point level smoothers (ordered after the calls queued so far) */
+int fmx_wb_scan_reset(void *scan);
+int fmx_wb_scan_process(void *scan, const void *d_wide, int n_out, fmx_signal_level *d_level);
+/* host only: validates the configuration and writes the first min(cap, n_points)
+ * point frequencies (freq_hz may be NULL).  Returns n_points (negative on error). */
+int fmx_wb_scan_points(const fmx_wb_scan_config *cfg, int *freq_hz, int cap);
+/* host only: point p is a peak when dbfs[p] >= min_dbfs, dbfs[p] > dbfs[q] for
+ * p - min_spacing <= q < p and dbfs[p] >= dbfs[q] for p < q <= p + min_spacing
+ * (a tie goes to the lowest index).  Writes the first min(cap, count) indices,
+ * ascending; returns the count (negative on error). */
+int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int min_spacing, int *idx, int cap);
 
 /* ---- device memory helpers (so C/FFI callers need no HIP headers) ---- */
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes);

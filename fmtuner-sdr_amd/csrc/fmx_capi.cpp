@@ -157,6 +157,7 @@ struct Handle {
   // until the next RDS call): the ring refill's source (FmxRdsState::ring_ok)
   int rds_last_buf = -1;
   int ring_always = 0; // fmx_diag_set(FMX_DIAG_RDS_RING_ALWAYS): k_rds writes the ring every call
+  int fe_generic = 0;  // fmx_diag_set(FMX_DIAG_FE_GENERIC): fmx_wb_process_block's front end is k_frontend for every n
   // the call's PSK2 symbols, k_rds (sC) -> k_bits (sD), per slot (at most one
   // per decimation period)
   float *rds_sym[FMX_NBUF] = {}, *rds_sym_im[FMX_NBUF] = {};
@@ -1088,8 +1089,10 @@ static void step_done(Handle *h, bool stereo_hist_written) {
 
 // the values of one process_block step that its four streams share
 struct Step {
-  const uint8_t *d_iq;
+  const uint8_t *d_iq;    // u8 IQ rows (fmx_process_block), or
   size_t iq_stride;
+  const float *cf;        // complex-float rows at the DSP rate (fmx_wb_process_block; d_iq null)
+  int cf_stride;          // in floats
   int n;
   const fmx_block_out *o; // the outputs
   bool stereo, rds;
@@ -1134,9 +1137,12 @@ static int step_sA(Handle *h, Step &s) {
   const unsigned spec16 = s.rds ? tset_speculate(h, h->t_rds, s.n, nrslot, static_cast<size_t>(h->C) * 256) : 0u;
   // ---- front end (sA) ----
   {
-    FeArgs a = fe_args(h, s.n, h->M > 1 ? FE_IN_U8_DECIM : FE_IN_U8_DIRECT, s.buf);
+    const bool cf = s.cf != nullptr;
+    FeArgs a = fe_args(h, s.n, cf ? FE_IN_CF : (h->M > 1 ? FE_IN_U8_DECIM : FE_IN_U8_DIRECT), s.buf);
     a.iq = s.d_iq;
     a.iq_stride = s.iq_stride;
+    a.in_f = s.cf;
+    a.in_stride = s.cf_stride;
     a.mpx_out = s.mpx;
     a.mpx_stride = s.mpx_stride;
     a.do_demod = 1;
@@ -1159,10 +1165,17 @@ static int step_sA(Handle *h, Step &s) {
     // groups.  Any other caller geometry keeps the resampler inside k_fe8
     // (its RS = true instance, scalar MPX stores): correct, slower.
     const bool mpx_vec16 = ((reinterpret_cast<uintptr_t>(s.mpx) | (static_cast<uintptr_t>(s.mpx_stride) * 4)) & 15) == 0;
-    s.use_rs = s.rds && h->hdes->rds_del <= 2.1f && h->t_rds.G == 1 && fe8 && mpx_vec16;
-    // the pilot BPF of a k_fe8 step runs as k_pilot (after it, on sA): k_fe8
-    // writes the MPX and the stereo history rows k_pilot starts from
-    s.pil_k = s.stereo && fe8;
+    const bool rs_ok = s.rds && h->hdes->rds_del <= 2.1f && h->t_rds.G == 1 && mpx_vec16;
+    // complex-float rows: k_fecf, which like k_fe8's RS = false instance has
+    // no resampler inside -- an RDS step whose resampler cannot run as k_rs
+    // takes k_frontend (FE_IN_CF, pilot BPF and resampler inside), as every
+    // call shape k_fecf does not take and every call under FMX_DIAG_FE_GENERIC
+    const bool fecf = cf && !h->fe_generic && fecf_ok(a) && (!s.rds || rs_ok);
+    const bool fast = fe8 || fecf;
+    s.use_rs = rs_ok && fast;
+    // the pilot BPF of a k_fe8 / k_fecf step runs as k_pilot (after it, on sA): the front
+    // end writes the MPX and the stereo history rows k_pilot starts from
+    s.pil_k = s.stereo && fast;
     if (s.pil_k) {
       a.pilot_out = nullptr;
       a.st_hist_out = 1;
@@ -1188,8 +1201,9 @@ static int step_sA(Handle *h, Step &s) {
       if ((rc = launch_reset_parts(h, RSP_RDS, h->sA)) != FMX_OK) return rc;
       s.rds_reset_on_a = true;
     }
-    KBind t(h, fe8 ? FMX_K_FRONTEND : FMX_K_FRONTEND_GENERIC, h->sA, s.evFE);
-    if ((rc = launch_frontend_m(a, h->M, h->hdes->dec_tpp, h->sA, dec_warm(h))) != FMX_OK) {
+    KBind t(h, fast ? FMX_K_FRONTEND : FMX_K_FRONTEND_GENERIC, h->sA, s.evFE);
+    rc = fecf ? launch_fecf(a, h->sA) : launch_frontend_m(a, h->M, h->hdes->dec_tpp, h->sA, dec_warm(h));
+    if (rc != FMX_OK) {
       h->err = "frontend launch failed";
       h->t_rds.spec = false; // the next step's schedule was not copied
       return rc;
@@ -1487,13 +1501,16 @@ int fmx_host_stats(void *handle, double *out, int n) {
 int fmx_diag_set(void *handle, int what, int value) {
   Handle *h = H(handle);
   if (!h) return FMX_E_INVALID;
-  if (what != FMX_DIAG_RDS_RING_ALWAYS) {
+  if (what == FMX_DIAG_RDS_RING_ALWAYS) h->ring_always = value != 0;
+  else if (what == FMX_DIAG_FE_GENERIC) h->fe_generic = value != 0;
+  else {
     h->err = "unknown diagnostic setting";
     return FMX_E_INVALID;
   }
-  h->ring_always = value != 0;
   return FMX_OK;
 }
+
+int fmx_diag_lds_bytes(int which) { return fe_launch_lds_bytes(which) < 0 ? FMX_E_INVALID : fe_launch_lds_bytes(which); }
 
 int fmx_diag_rds_ring(void *handle, int channel, float *out) {
   Handle *h = H(handle);
@@ -1914,6 +1931,12 @@ struct Wb {
   uint16_t *stage = nullptr;
   hipEvent_t ev = nullptr;
   bool ev_set = false;
+  // fmx_wb_process_block's rows [C][rows_stride] complex float (allocated on
+  // first use, 16-B aligned, an even stride).  One buffer: k_wb writes it and
+  // the front end reads it, both on sA and in order, so the next call's k_wb
+  // starts after this call's front end has ended; nothing else reads it.
+  float *d_rows = nullptr;
+  int rows_stride = 0; // complex samples
 };
 Wb *W(void *p) { return static_cast<Wb *>(p); }
 size_t wb_sample_bytes(const WbPlan &p) { return p.format == FMX_WB_S16 ? 4 : 2; }
@@ -1924,8 +1947,10 @@ void wb_free(Wb *w) {
     if (b) hipFree(b);
   if (w->stage) hipHostFree(w->stage);
   if (w->ev) hipEventDestroy(w->ev);
+  if (w->d_rows) hipFree(w->d_rows);
   delete w;
 }
+int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, const char *who);
 } // namespace
 
 int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, int n_channels, void **wb) {
@@ -2036,6 +2061,74 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
   if (n_out == 0) return FMX_OK;
   int rc;
   if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  return wb_run(w, d_wide, n_out, d_out, out_stride, "fmx_wb_process");
+}
+
+int fmx_wb_process_block(void *wb, const void *d_wide, int n, const fmx_block_out *o) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  Handle *h = w->h;
+  const WbPlan &p = w->p;
+  const char *bad = nullptr;
+  if (h->M != 1) bad = "the handle's iq_rate must equal its dsp_rate";
+  else if (p.fs / p.D != h->cfg.dsp_rate) bad = "the channelizer's dsp_rate is not the handle's";
+  else if (w->C != h->C) bad = "the channelizer's channel count is not the handle's";
+  else if (n < 0 || (n > 0 && !d_wide)) bad = "null input or negative n";
+  else if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count) bad = "d_pcm_l, d_pcm_r and d_pcm_count are required";
+  else if (o->d_signal) bad = "d_signal must be NULL (a station's RF level in a shared capture is the band scan's)";
+  if (bad) {
+    h->err = std::string("fmx_wb_process_block: ") + bad;
+    return FMX_E_INVALID;
+  }
+  if (n > std::min(h->cfg.block, p.block)) {
+    h->err = "fmx_wb_process_block: n exceeds the handle's or the channelizer's block";
+    return FMX_E_CAPACITY;
+  }
+  if (n == 0) return FMX_OK;
+  int rc;
+  if (!w->d_rows) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int stride = (p.block + 1) & ~1;
+    if (hipMalloc(reinterpret_cast<void **>(&w->d_rows), static_cast<size_t>(w->C) * stride * 2 * sizeof(float)) != hipSuccess) {
+      w->d_rows = nullptr;
+      h->err = "fmx_wb_process_block: hipMalloc failed";
+      return FMX_E_NOMEM;
+    }
+    w->rows_stride = stride;
+  }
+  // as process_block, with the channelizer ahead of the front end on sA: no
+  // join, the resets of queued fmx_reset / fmx_retune calls through the
+  // pending lists
+  if ((rc = prepare_pipelined(h)) != FMX_OK) return rc;
+  if (h->timing) harvest_timing(h);
+  if ((rc = wb_run(w, d_wide, n, w->d_rows, w->rows_stride, "fmx_wb_process_block")) != FMX_OK) return rc;
+  Step s{};
+  s.cf = w->d_rows;
+  s.cf_stride = 2 * w->rows_stride;
+  s.n = n;
+  s.o = o;
+  s.stereo = h->cfg.stereo != 0;
+  s.rds = h->cfg.rds != 0;
+  s.buf = static_cast<int>(h->step % FMX_NBUF);
+  s.mpx = o->d_mpx ? o->d_mpx : h->mpx[s.buf];
+  s.mpx_stride = o->d_mpx ? o->mpx_stride : h->row;
+  s.evFE = h->evF[h->step % FMX_FRING];
+  if ((rc = step_sA(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sC(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sB(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sD(h, s)) != FMX_OK) return rc;
+  h->block_index++;
+  step_done(h, s.stereo);
+  return FMX_OK;
+}
+
+// k_wb (and the history kernel) of one call on sA, and the object's history,
+// valid, counter and cur past it: fmx_wb_process and fmx_wb_process_block
+namespace {
+int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, const char *who) {
+  Handle *h = w->h;
+  const WbPlan &p = w->p;
+  int rc;
   WbArgs a{};
   a.in = d_wide;
   a.s16 = p.format == FMX_WB_S16;
@@ -2056,7 +2149,7 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
   a.out = d_out;
   a.out_stride = out_stride;
   if ((rc = launch_wb(a, h->sA)) != FMX_OK) {
-    h->err = "fmx_wb_process: kernel launch failed";
+    h->err = std::string(who) + ": kernel launch failed";
     return rc;
   }
   const int64_t n_in = static_cast<int64_t>(n_out) * p.D;
@@ -2065,6 +2158,7 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
   w->counter += static_cast<uint64_t>(n_in);
   return FMX_OK;
 }
+} // namespace
 
 /* ---- band scan (fmx.h; kernels in fmx_wb_scan.inc) ---- */
 namespace {

@@ -209,6 +209,12 @@ void set_launch_events(void *start, void *stop);
 int launch_frontend_m(const FeArgs &a, int M, int tpp, void *stream, bool vec = false);
 // whether launch_frontend_m would run k_fe8 for these arguments
 bool frontend_is_fe8(const FeArgs &a, int M, int tpp);
+// k_fecf (fmx_fecf.inc): the fast front end on complex-float rows at the DSP
+// rate (fmx_wb_process_block); fecf_ok: whether it takes these arguments --
+// every other FE_IN_CF call runs k_frontend (launch_frontend_m(a, 1, 1, ...))
+bool fecf_ok(const FeArgs &a);
+int launch_fecf(const FeArgs &a, void *stream);
+int fe_launch_lds_bytes(int which); // fmx_diag_lds_bytes
 int launch_pll(const PllArgs &a, void *stream);
 int launch_pilot(const PilotArgs &a, void *stream);
 int launch_audio(const AudioArgs &a, void *stream);

@@ -3888,4 +3888,5 @@ int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sa
 }
 #include "fmx_wb.inc"
 #include "fmx_wb_scan.inc"
+#include "fmx_fecf.inc"
 } // namespace fmx

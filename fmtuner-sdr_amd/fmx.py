@@ -19,6 +19,7 @@ PARAM = dict(bandwidth_hz=1, w0_hz=2, deemphasis=3, dsp_agc=4, blend=5,
              force_mono=6, force_stereo=7, bandwidth_mode=8, deemph_us=9, deviation_hz=10)
 K_FRONTEND, K_STEREO, K_AUDIO, K_RDS, K_RS, K_PILOT, K_FRONTEND_GENERIC, K_BITS = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ["frontend", "stereo", "audio", "rds", "rs", "pilot", "frontend_generic", "bits"]
+FMX_DIAG_RDS_RING_ALWAYS, FMX_DIAG_FE_GENERIC = 1, 2
 
 
 class Config(C.Structure):
@@ -113,6 +114,8 @@ def lib():
         "fmx_wb_set_freq": (i, [vp, i, i]),
         "fmx_wb_reset": (i, [vp, C.c_int64]),
         "fmx_wb_process": (i, [vp, vp, i, vp, i]),
+        "fmx_wb_process_block": (i, [vp, vp, i, C.POINTER(BlockOut)]),
+        "fmx_diag_lds_bytes": (i, [i]),
         "fmx_wb_weights": (i, [C.POINTER(WbConfig), i, fp, i]),
         "fmx_wb_scan_create": (i, [vp, C.POINTER(WbScanConfig), C.POINTER(vp)]),
         "fmx_wb_scan_destroy": (i, [vp]),
@@ -284,7 +287,8 @@ class Handle:
         return {KERNEL_NAMES[k]: (ms[k], cnt[k]) for k in range(nk)}
 
     def diag_set(self, what, value):
-        """fmx_diag_set: what 1 = k_rds writes the RDS ring every call."""
+        """fmx_diag_set: what 1 = k_rds writes the RDS ring every call, 2 =
+        Wideband.process_block takes the generic front end for every n."""
         self._ck(self.L.fmx_diag_set(self.h, what, value), "fmx_diag_set")
 
     def diag_rds_ring(self, channel):
@@ -350,6 +354,13 @@ class Wideband:
         """d_wide: n_out * D interleaved I/Q samples; d_out: [n][out_stride] complex float."""
         self._ck(self.L.fmx_wb_process(self.w, C.c_void_p(d_wide), n_out, C.c_void_p(d_out), out_stride),
                  "fmx_wb_process")
+
+    def process_block(self, d_wide, n, out):
+        """The band receiver in one call (fmx_wb_process_block): n * D wide
+        samples in, Handle.process_block's outputs (a BlockOut, d_signal None)
+        for every channel; queued, valid after Handle.sync()."""
+        self._ck(self.L.fmx_wb_process_block(self.w, C.c_void_p(d_wide), n, C.byref(out)),
+                 "fmx_wb_process_block")
 
 
 def wb_weights(wcfg, freq_hz):

@@ -47,13 +47,14 @@
 extern "C" {
 #endif
 
-/* ABI history: 11 adds the band scan (fmx_wb_scan_*, fmx_scan_peaks: one wide IQ capture in, the RF
+/* ABI history: 12 adds the one-call band receiver (fmx_wb_process_block: one wide IQ capture in, every
+ * station's audio, stereo state and RDS groups out), FMX_DIAG_FE_GENERIC and fmx_diag_lds_bytes; 11 adds the band scan (fmx_wb_scan_*, fmx_scan_peaks: one wide IQ capture in, the RF
  * level of every scan point out); 10 adds the wideband channelizer (fmx_wb_*: one wide IQ capture in, every tuned
  * channel's baseband out); 9 (round 6) adds fmx_diag_set / fmx_diag_rds_ring and fmx_build_info; 8 (round 5) adds FMX_K_BITS (FMX_K_COUNT 8); 7 (round 5) adds fmx_host_stats and FMX_K_FRONTEND_GENERIC (FMX_K_COUNT 7); 6 (round 4) adds FMX_K_PILOT (FMX_K_COUNT 6); 5 (round 4) added FMX_K_RS (FMX_K_COUNT 5; fmx_kernel_times
  * fills at most n entries); 4 (round 3) added fmx_synth_config.level_spread_db,
  * which changed that struct's size: callers must be rebuilt against this
  * header. */
-#define FMX_ABI_VERSION 11
+#define FMX_ABI_VERSION 12
 
 enum {
   FMX_OK = 0,
@@ -252,6 +253,30 @@ int fmx_wb_set_freq(void *wb, int channel, int freq_hz);
 int fmx_wb_reset(void *wb, int64_t sample0);
 /* consumes n_out * D wide samples (n_out <= block, else FMX_E_CAPACITY) */
 int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int out_stride);
+/* The band receiver in one call: one reference block (main.cpp:1239-1308) for
+ * every channel of the channelizer.  Consumes n * D wide samples; the outputs
+ * are fmx_process_block's for a handle whose decimator had produced the
+ * channelizer's rows: PCM (clamped; fmx_retune's fade and mute apply), counts,
+ * stereo flag, pilot tenths, stereo indicator, RDS groups and counts, d_mpx;
+ * stereo and RDS as the handle's config says.  d_clip_ratio is
+ * FMDemod::getClippingRatio of processSplitComplex on the rows (the share of
+ * the call's n samples with |re| or |im| >= 0.995).  d_signal must be NULL
+ * (FMX_E_INVALID otherwise): the RF level of a station in a shared capture is
+ * the band scan's definition above, and a scan object with its points at the
+ * station frequencies delivers it from the same capture.
+ * Conditions: the handle has iq_rate == dsp_rate, the channelizer that
+ * dsp_rate and the handle's channel count (FMX_E_INVALID otherwise, the
+ * message names this function); n <= min(the handle's block, the
+ * channelizer's), else FMX_E_CAPACITY; d_pcm_l, d_pcm_r and d_pcm_count are
+ * required; n == 0 does nothing.  Queued like fmx_process_block, on the same
+ * four streams and without draining them: calls may be queued ahead, and
+ * fmx_reset / fmx_retune / fmx_wb_set_freq between queued calls take effect
+ * at the next call.  The channelizer's history and sample counter advance as
+ * in fmx_wb_process, and a stream may mix the two calls; the rows themselves
+ * stay inside the object (fmx_wb_process returns them).  Calls of n >= 1024
+ * with n % 4 == 0 run the fast front end (k_fecf, then k_pilot / k_rs as after
+ * k_fe8); every other n >= 1 is correct on the generic one. */
+int fmx_wb_process_block(void *wb, const void *d_wide, int n, const fmx_block_out *out);
 /* host only: the channel weights W[k] = 2 fc h[k] exp(+j 2 pi f k / wide_rate),
  * k = 0..L-1, as 2L floats (re, im) read back from the kernel's f16 hi + lo
  * tables.  Returns 2L (negative on error). */
@@ -318,7 +343,8 @@ int fmx_memset(void *handle, void *d_ptr, int value, size_t bytes);
  * launch counts per kernel id since the last reset. */
 enum {
   FMX_K_FRONTEND = 0, /* decimate + DC + IQ FIR + AGC + discriminator (+ pilot BPF, + RDS
-                         resample when process_block does not run them as kernels of their own) */
+                         resample when process_block does not run them as kernels of their own);
+                         fmx_wb_process_block's k_fecf counts here (k_wb is not timed)           */
   FMX_K_STEREO = 1,   /* pilot PLL + blend + L-R matrix (one lane per channel)                 */
   FMX_K_AUDIO = 2,    /* L/R 15 kHz FIRs + 32 kHz resampler + de-emphasis + DC + clamp         */
   FMX_K_RDS = 3,      /* 57 kHz BPSK demod + symsync (+ biphase + block sync in fmx_rds)        */
@@ -327,8 +353,8 @@ enum {
   FMX_K_PILOT = 5,    /* the 19 kHz pilot BPF when process_block runs it as its own kernel
                          (k_pilot, on the front-end stream after k_fe8)                         */
   FMX_K_FRONTEND_GENERIC = 6, /* process_block's front end when it runs as the generic k_frontend
-                         (calls of n < 1024 samples, unaligned IQ rows) instead of k_fe8;
-                         FMX_K_FRONTEND then counts k_fe8 launches only                           */
+                         (calls of n < 1024 samples, unaligned IQ rows) instead of k_fe8 (of k_fecf in
+                         fmx_wb_process_block); FMX_K_FRONTEND then counts k_fe8 / k_fecf launches only */
   FMX_K_BITS = 7,     /* process_block's RDS bit decoders (biphase, delta, block sync, groups:
                          k_bits, on the audio stream ahead of k_audio)                          */
   FMX_K_COUNT = 8
@@ -353,8 +379,16 @@ int fmx_host_stats(void *handle, double *out, int n);
  * 1) makes k_rds write it every call (round 5's behaviour; the test arm);
  * fmx_diag_rds_ring copies the channel's ring, oldest sample first, as 256
  * (re, im) float pairs to host memory (synchronous; refills it first). */
-enum { FMX_DIAG_RDS_RING_ALWAYS = 1 };
+/* fmx_diag_set(FMX_DIAG_FE_GENERIC, 1) makes fmx_wb_process_block take the
+ * generic front end (k_frontend on the rows) for every n: the A/B arm of
+ * tools/bench_band_receiver.py and a test arm; no effect on any other call. */
+enum { FMX_DIAG_RDS_RING_ALWAYS = 1, FMX_DIAG_FE_GENERIC = 2 };
 int fmx_diag_set(void *handle, int what, int value);
+/* host only: the dynamic LDS bytes a front-end launch takes on top of the
+ * kernel's static LDS (which the code object records): which 0 = k_fe8 at
+ * M = 10 with k_rs behind it (fmx_process_block at 2.4 MS/s), 1 = k_fecf.
+ * tests/test_fecf_resources.py compares the two kernels' totals. */
+int fmx_diag_lds_bytes(int which);
 int fmx_diag_rds_ring(void *handle, int channel, float *out);
 
 /* ---- synthetic IQ (bench / tests input; see fmx_synth.h) ---- */

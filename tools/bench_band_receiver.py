@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Times the band receiver: one wide IQ capture in, every station's audio,
+stereo state and RDS groups out, three ways in one process --
+
+  A  fmx_wb_process_block (k_wb -> k_fecf -> k_pilot | k_rs -> k_rds | k_pll |
+     k_bits -> k_audio on the pipelined step's four streams);
+  B  the same call with FMX_DIAG_FE_GENERIC (k_frontend on the rows instead of
+     k_fecf / k_pilot / k_rs);
+  C  the route before that call existed: fmx_wb_process -> fmx_demod ->
+     fmx_stereo -> fmx_afpost -> fmx_rds, five stage calls on one stream.
+
+Warm-up calls per arm, then --reps repetitions that alternate a train of
+--train calls per arm, each train ending in one fmx_sync.  The calls run on
+the handle's own streams, which the ABI does not hand out, so the clock is the
+host's around the synchronised train; per-call time = train time / calls.
+Median and min-max over the repetitions, plus fmx_kernel_times of a train of
+arm A (k_wb is not timed).
+
+Cases: the band of tools/bench_channelizer.py -- int16, D = 100 (24 MS/s), 28
+taps per phase, 205 channels at 100 kHz, 4096 outputs per call (17.07 ms of
+signal), stereo + RDS -- and a slice: D = 10 (2.4 MS/s), 5 channels.
+
+Writes one JSON document (default profiles/wb_receiver.json) and exits
+non-zero when, in the band case, A's median is not below C's or A is not
+faster than real time.  The slice is reported, not gated: five channels are
+launch latency.  Needs a GPU."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "fmtuner-sdr_amd"))
+
+DSP = 240_000
+N_OUT = 4096
+TPP = 28
+GS = 8
+
+
+def _stats(ms):
+    import numpy as np
+    ms = np.sort(np.array(ms))
+    return dict(median=float(np.median(ms)), min=float(ms[0]), max=float(ms[-1]))
+
+
+def run_case(fmx, torch, name, D, channels, step, warmup, reps, train):
+    Fs, C, n = D * DSP, channels, N_OUT
+    freqs = [-int((C - 1) * step / 2) + i * step for i in range(C)]
+    h = fmx.Handle(fmx.make_config(iq_rate=DSP, dsp_rate=DSP, block=n), C)
+    wb = fmx.Wideband(h, fmx.make_wb_config(Fs, DSP, fmx.FMX_WB_S16, TPP, n), freqs)
+    dev = torch.device("cuda")
+    g = torch.Generator(device="cpu").manual_seed(1)
+    raw = torch.randint(-32768, 32768, (2 * n * D,), generator=g, dtype=torch.int32).to(torch.int16).to(dev)
+    f = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)  # noqa: E731
+    z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)  # noqa: E731
+    # three rotating output sets of the one-call arms, as bench.py rotates them
+    T = dict(pl=f(3, C, n), pr=f(3, C, n), clip=f(3, C), cnt=z(3, C), st=z(3, C), pil=z(3, C), ind=z(3, C),
+             gcnt=z(3, C), grp=z(3, C, GS, 4))
+    outs = [fmx.BlockOut(None, 0, T["pl"][k].data_ptr(), T["pr"][k].data_ptr(), n, T["cnt"][k].data_ptr(),
+                         T["st"][k].data_ptr(), T["pil"][k].data_ptr(), T["clip"][k].data_ptr(),
+                         T["grp"][k].data_ptr(), GS, T["gcnt"][k].data_ptr(), None, T["ind"][k].data_ptr())
+            for k in range(3)]
+    # the stage chain's buffers
+    bb, mpx, lf, rf, sl, sr = f(C, 2 * n), f(C, n), f(C, n), f(C, n), f(C, n), f(C, n)
+    s_st, s_pil, s_cnt, s_gcnt, s_grp = z(C), z(C), z(C), z(C), z(C, GS, 4)
+    torch.cuda.synchronize()
+    calls = [0]
+
+    def one_call():
+        wb.process_block(raw.data_ptr(), n, outs[calls[0] % 3])
+        calls[0] += 1
+
+    def stage_chain():
+        wb.process(raw.data_ptr(), n, bb.data_ptr(), n)
+        h.demod(bb.data_ptr(), 2 * n, n, mpx.data_ptr(), n)
+        h.stereo(mpx.data_ptr(), n, n, lf.data_ptr(), rf.data_ptr(), n, s_st.data_ptr(), s_pil.data_ptr())
+        h.afpost(lf.data_ptr(), rf.data_ptr(), n, n, sl.data_ptr(), sr.data_ptr(), n, n, s_cnt.data_ptr())
+        h.rds(mpx.data_ptr(), n, n, s_grp.data_ptr(), GS, s_gcnt.data_ptr())
+
+    arms = {"A_one_call": (0, one_call), "B_one_call_generic_front_end": (1, one_call), "C_stage_calls": (0, stage_chain)}
+
+    def run_train(generic, fn, k):
+        h.diag_set(fmx.FMX_DIAG_FE_GENERIC, generic)
+        h.sync()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            fn()
+        h.sync()
+        return (time.perf_counter() - t0) * 1e3 / k
+
+    for generic, fn in arms.values():
+        run_train(generic, fn, warmup)
+    ms = {k: [] for k in arms}
+    for _ in range(reps):
+        for k, (generic, fn) in arms.items():
+            ms[k].append(run_train(generic, fn, train))
+    h.diag_set(fmx.FMX_DIAG_FE_GENERIC, 0)
+    h.timing_enable(True)
+    run_train(0, one_call, train)
+    kt = h.kernel_times()
+    h.timing_enable(False)
+    assert bool(torch.isfinite(T["pl"]).all()) and bool(torch.isfinite(sl).all())
+    assert int(T["cnt"].min()) > 0 and int(s_cnt.min()) > 0
+    wb.close()
+    h.close()
+    signal_ms = n / DSP * 1e3
+    res = dict(case=name, format="s16", D=D, wide_rate=Fs, taps=D * TPP, channels=C, step_hz=step, n_out=n,
+               stereo=1, rds=1, warmup=warmup, reps=reps, calls_per_train=train, signal_ms=signal_ms)
+    for k in arms:
+        st = _stats(ms[k])
+        res[k] = dict(ms_per_call=st, times_real_time=signal_ms / st["median"])
+    res["A_over_C"] = res["A_one_call"]["ms_per_call"]["median"] / res["C_stage_calls"]["ms_per_call"]["median"]
+    res["A_over_B"] = (res["A_one_call"]["ms_per_call"]["median"] /
+                       res["B_one_call_generic_front_end"]["ms_per_call"]["median"])
+    res["kernel_ms_per_launch_arm_A"] = {k: (v[0] / v[1] if v[1] else None) for k, v in kt.items()}
+    res["kernel_launches_arm_A"] = {k: v[1] for k, v in kt.items()}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--train", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wb_receiver.json"))
+    a = ap.parse_args()
+    if a.reps < 10:
+        ap.error("--reps must be at least 10")
+    import torch
+    import fmx
+    if not torch.cuda.is_available():
+        sys.exit("bench_band_receiver: no GPU")
+    cases = [run_case(fmx, torch, "band_24MSps_205ch_100kHz", 100, 205, 100_000, a.warmup, a.reps, a.train),
+             run_case(fmx, torch, "slice_2.4MSps_5ch", 10, 5, 400_000, a.warmup, a.reps, a.train)]
+    doc = dict(tool="tools/bench_band_receiver.py", library=fmx.build_info(), device=torch.cuda.get_device_name(0),
+               cases=cases)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc))
+    band = cases[0]
+    if band["A_over_C"] >= 1.0:
+        sys.exit("bench_band_receiver: the one call is not faster than the five stage calls in the band case")
+    if band["A_one_call"]["times_real_time"] <= 1.0:
+        sys.exit("bench_band_receiver: the band case is slower than real time")
+
+
+if __name__ == "__main__":
+    main()

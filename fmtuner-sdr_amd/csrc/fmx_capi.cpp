@@ -1934,9 +1934,21 @@ struct Wb {
   // fmx_wb_process_block's rows [C][rows_stride] complex float (allocated on
   // first use, 16-B aligned, an even stride).  One buffer: k_wb writes it and
   // the front end reads it, both on sA and in order, so the next call's k_wb
-  // starts after this call's front end has ended; nothing else reads it.
+  // starts after this call's front end has ended.  Its one other reader is
+  // fmx_wb_signal's k_wb_level, queued on sA as well: behind the front end of
+  // the call it measures, ahead of the next call's k_wb.
   float *d_rows = nullptr;
   int rows_stride = 0; // complex samples
+  // fmx_wb_signal: the most recent non-empty call (wb_run records it) --
+  // its input, its rows (d_rows or the caller's d_out) and their stride --
+  // and whether it has been measured yet
+  const void *sig_wide = nullptr;
+  const float *sig_rows = nullptr;
+  int sig_stride = 0, sig_n = 0;
+  bool sig_pending = false;
+  uint32_t *d_clip = nullptr; // [clip workgroups of a full block][2] (allocated on first use)
+  float *d_sm = nullptr;      // [C][2] level smoothers
+  double sp[4] = {0.0, -4.0, -55.0, -19.0}; // gain*factor, bias, floor, ceil
 };
 Wb *W(void *p) { return static_cast<Wb *>(p); }
 size_t wb_sample_bytes(const WbPlan &p) { return p.format == FMX_WB_S16 ? 4 : 2; }
@@ -1948,6 +1960,8 @@ void wb_free(Wb *w) {
   if (w->stage) hipHostFree(w->stage);
   if (w->ev) hipEventDestroy(w->ev);
   if (w->d_rows) hipFree(w->d_rows);
+  if (w->d_clip) hipFree(w->d_clip);
+  if (w->d_sm) hipFree(w->d_sm);
   delete w;
 }
 int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, const char *who);
@@ -1985,6 +1999,8 @@ int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, in
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->d_w), rows.size() * sizeof(uint16_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_fpos), fpos.size() * sizeof(uint32_t));
   for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&w->d_hist[b], hist_bytes);
+  const size_t sm_bytes = static_cast<size_t>(n_channels) * 2 * sizeof(float);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_sm), sm_bytes);
   if (e != hipSuccess) {
     h->err = std::string("fmx_wb_create: hipMalloc failed: ") + hipGetErrorString(e);
     wb_free(w);
@@ -1995,6 +2011,8 @@ int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, in
   // synchronous copies: the tables are complete before the first call is queued
   if (e == hipSuccess) e = hipMemcpy(w->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(w->d_fpos, fpos.data(), fpos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  // the smoothers' only readers run on sA: cleared there, ahead of the first of them
+  if (e == hipSuccess) e = hipMemsetAsync(w->d_sm, 0, sm_bytes, h->sA);
   if (e != hipSuccess) {
     h->err = std::string("fmx_wb_create: ") + hipGetErrorString(e);
     wb_free(w);
@@ -2075,7 +2093,7 @@ int fmx_wb_process_block(void *wb, const void *d_wide, int n, const fmx_block_ou
   else if (w->C != h->C) bad = "the channelizer's channel count is not the handle's";
   else if (n < 0 || (n > 0 && !d_wide)) bad = "null input or negative n";
   else if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count) bad = "d_pcm_l, d_pcm_r and d_pcm_count are required";
-  else if (o->d_signal) bad = "d_signal must be NULL (a station's RF level in a shared capture is the band scan's)";
+  else if (o->d_signal) bad = "d_signal must be NULL (fmx_wb_signal, called behind this call, delivers every station's RF level)";
   if (bad) {
     h->err = std::string("fmx_wb_process_block: ") + bad;
     return FMX_E_INVALID;
@@ -2156,9 +2174,87 @@ int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, c
   w->cur ^= 1;
   w->valid = static_cast<int>(std::min<int64_t>(p.L - 1, w->valid + n_in));
   w->counter += static_cast<uint64_t>(n_in);
+  // the call fmx_wb_signal measures
+  w->sig_wide = d_wide;
+  w->sig_rows = d_out;
+  w->sig_stride = out_stride;
+  w->sig_n = n_out;
+  w->sig_pending = true;
   return FMX_OK;
 }
 } // namespace
+
+int fmx_wb_signal(void *wb, fmx_signal_level *d_level) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  Handle *h = w->h;
+  const WbPlan &p = w->p;
+  const char *bad = nullptr;
+  if (!d_level) bad = "null d_level";
+  else if (reinterpret_cast<uintptr_t>(d_level) & 7) bad = "d_level is not 8-byte aligned";
+  else if (!w->sig_rows) bad = "no fmx_wb_process / fmx_wb_process_block call of n >= 1 to measure yet";
+  else if (!w->sig_pending) bad = "the most recent call has been measured (one level per call: a smoother advances once)";
+  if (bad) {
+    h->err = std::string("fmx_wb_signal: ") + bad;
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (!w->d_clip) {
+    const size_t n_clip = static_cast<size_t>(wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D)) * 2;
+    if (hipMalloc(reinterpret_cast<void **>(&w->d_clip), n_clip * sizeof(uint32_t)) != hipSuccess) {
+      w->d_clip = nullptr;
+      h->err = "fmx_wb_signal: hipMalloc failed";
+      return FMX_E_NOMEM;
+    }
+  }
+  // on sA alone, behind the call it measures: no join, the other streams keep running
+  WbLevelArgs a{};
+  a.rows = w->sig_rows;
+  a.stride = w->sig_stride;
+  a.n = w->sig_n;
+  a.C = w->C;
+  a.in = w->sig_wide;
+  a.s16 = p.format == FMX_WB_S16;
+  a.D = p.D;
+  a.clip = w->d_clip;
+  a.sm = w->d_sm;
+  a.level = d_level;
+  for (int k = 0; k < 4; ++k) a.sp[k] = w->sp[k];
+  int rc;
+  if ((rc = launch_wb_level(a, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_signal: kernel launch failed";
+    return rc;
+  }
+  w->sig_pending = false;
+  return FMX_OK;
+}
+
+int fmx_wb_set_signal_params(void *wb, int applied_gain_db, double gain_comp_factor, double bias_db, double floor_dbfs,
+                             double ceil_dbfs) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  // computeSignalLevel: compensated = (dbfs - gain * factor) + bias; the values travel with each launch
+  w->sp[0] = static_cast<double>(applied_gain_db) * gain_comp_factor;
+  w->sp[1] = bias_db;
+  w->sp[2] = floor_dbfs;
+  w->sp[3] = ceil_dbfs;
+  return FMX_OK;
+}
+
+int fmx_wb_signal_reset(void *wb, int channel) {
+  Wb *w = W(wb);
+  if (!w) return FMX_E_INVALID;
+  Handle *h = w->h;
+  if (channel < -1 || channel >= w->C) {
+    h->err = "fmx_wb_signal_reset: channel out of range";
+    return FMX_E_INVALID;
+  }
+  // on sA: behind the level calls queued so far, ahead of later ones
+  const size_t one = 2 * sizeof(float);
+  if (channel < 0) HIP_TRY(hipMemsetAsync(w->d_sm, 0, one * static_cast<size_t>(w->C), h->sA));
+  else HIP_TRY(hipMemsetAsync(w->d_sm + 2 * static_cast<size_t>(channel), 0, one, h->sA));
+  return FMX_OK;
+}
 
 /* ---- band scan (fmx.h; kernels in fmx_wb_scan.inc) ---- */
 namespace {

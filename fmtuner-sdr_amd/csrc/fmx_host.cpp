@@ -11,6 +11,8 @@
 //                       the GPU every channel is a scan point measured in the
 //                       same block (fmx_signal_level.level120), so a sweep is
 //                       one gather instead of a retune loop
+//   fmx_xdr_signal_line XDRServer::updateSignal + buildSignalLine
+//                       (xdr_server.cpp:368-397): the "S" line of one station
 //   fmx_wav_header      AudioOutput::writeWAVHeader (audio_output.cpp:1346-1377)
 //   fmx_pcm_to_s16      AudioOutput::write's volume ramp (:1432-1467) and
 //                       writeWAVData's clamp + int16 conversion (:1379-1398)
@@ -127,6 +129,17 @@ int fmx_xdr_scan_line(const int *freq_khz, const double *level_sum, const int *r
     first = false;
   }
   if (!line.empty()) line = "U" + line; // XDRServer::pushScanLine
+  return copy_out(line, out, cap);
+}
+
+int fmx_xdr_signal_line(float level, int stereo, int forced_mono, int cci, int aci, char *out, int cap) {
+  // XDRServer::updateSignal (xdr_server.cpp:388-397): tenths, in float; a NaN level counts as 0
+  const float lv = level == level ? std::min(std::max(level, 0.0f), 120.0f) : 0.0f;
+  const int deci = static_cast<int>(std::round(lv * 10.0f));
+  // buildSignalLine (:368-386)
+  const char mode = forced_mono ? (stereo ? 'S' : 'M') : (stereo ? 's' : 'm');
+  char line[64];
+  std::snprintf(line, sizeof(line), "S%c%.1f,%d,%d\n", mode, deci / 10.0, cci, aci);
   return copy_out(line, out, cap);
 }
 

@@ -347,6 +347,20 @@ int wb_scan_workgroups(int n_out, int tpp, int nt);
 int wb_scan_clip_workgroups(long n_in);
 int launch_wb_scan(const WbScanArgs &a, void *stream);
 
+// ---- band receiver's RF level (fmx_wb_level.inc): the level of every channel from one call's rows ----
+struct WbLevelArgs {
+  const float *rows;       // [C][2 * stride] the call's complex rows (k_wb's output)
+  int stride, n, C;        // stride in complex samples, n outputs per channel
+  const void *in;          // the call's n * D wide samples, interleaved I/Q
+  int s16, D;              // as WbArgs
+  uint32_t *clip;          // [nclip][2] hard- and near-clipped samples (k_wb_scan_clip's)
+  float *sm;               // [C][2] smoother value, initialised flag
+  fmx_signal_level *level; // [C]
+  double sp[4];            // gain*factor, bias, floor, ceil
+  int nclip;               // clip workgroups (set by the launcher)
+};
+int launch_wb_level(const WbLevelArgs &a, void *stream);
+
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps
 

@@ -115,6 +115,9 @@ def lib():
         "fmx_wb_reset": (i, [vp, C.c_int64]),
         "fmx_wb_process": (i, [vp, vp, i, vp, i]),
         "fmx_wb_process_block": (i, [vp, vp, i, C.POINTER(BlockOut)]),
+        "fmx_wb_signal": (i, [vp, vp]),
+        "fmx_wb_set_signal_params": (i, [vp, i, C.c_double, C.c_double, C.c_double, C.c_double]),
+        "fmx_wb_signal_reset": (i, [vp, i]),
         "fmx_diag_lds_bytes": (i, [i]),
         "fmx_wb_weights": (i, [C.POINTER(WbConfig), i, fp, i]),
         "fmx_wb_scan_create": (i, [vp, C.POINTER(WbScanConfig), C.POINTER(vp)]),
@@ -142,6 +145,7 @@ def lib():
         "fmx_xdr_pi_reset": (None, [C.POINTER(XdrPiState)]),
         "fmx_xdr_rds_lines": (i, [C.POINTER(XdrPiState), vp, i, C.c_char_p, i]),
         "fmx_xdr_scan_line": (i, [vp, vp, vp, i, C.c_char_p, i]),
+        "fmx_xdr_signal_line": (i, [C.c_float, i, i, i, i, C.c_char_p, i]),
         "fmx_wav_header": (i, [C.c_uint32, vp]),
         "fmx_pcm_to_s16": (i, [vp, vp, i, i, C.POINTER(C.c_float), vp]),
         "fmx_iq_capture": (i, [C.c_char_p, vp, i, i]),
@@ -362,6 +366,22 @@ class Wideband:
         self._ck(self.L.fmx_wb_process_block(self.w, C.c_void_p(d_wide), n, C.byref(out)),
                  "fmx_wb_process_block")
 
+    def signal(self, d_level):
+        """fmx_wb_signal: the RF level of every channel from the rows of the
+        call just queued (process or process_block), once per call; d_level:
+        [n] fmx_signal_level (40 bytes each, 8-byte aligned).  Queued on the
+        stage stream, valid after Handle.sync()."""
+        self._ck(self.L.fmx_wb_signal(self.w, C.c_void_p(d_level)), "fmx_wb_signal")
+
+    def set_signal_params(self, applied_gain_db=0, gain_comp_factor=0.5, bias_db=-4.0, floor_dbfs=-55.0,
+                          ceil_dbfs=-19.0):
+        self._ck(self.L.fmx_wb_set_signal_params(self.w, applied_gain_db, gain_comp_factor, bias_db, floor_dbfs,
+                                                 ceil_dbfs), "fmx_wb_set_signal_params")
+
+    def signal_reset(self, channel=-1):
+        """Restarts one channel's level smoother (-1: every channel's)."""
+        self._ck(self.L.fmx_wb_signal_reset(self.w, channel), "fmx_wb_signal_reset")
+
 
 def wb_weights(wcfg, freq_hz):
     """fmx_wb_weights: W[k] as complex64 [L], read back from the f16 tables."""
@@ -523,6 +543,15 @@ def xdr_scan_line(freq_khz, level_sum, reads):
     rc = lib().fmx_xdr_scan_line(f.ctypes.data, s.ctypes.data, r.ctypes.data, len(f), buf, cap)
     if rc < 0:
         raise FmxError(f"fmx_xdr_scan_line failed ({rc})")
+    return buf.value.decode()
+
+
+def xdr_signal_line(level, stereo=False, forced_mono=False, cci=-1, aci=-1):
+    """fmx_xdr_signal_line: the XDR server's "S" line of one station (with its newline)."""
+    buf = C.create_string_buffer(64)
+    rc = lib().fmx_xdr_signal_line(float(level), int(bool(stereo)), int(bool(forced_mono)), int(cci), int(aci), buf, 64)
+    if rc < 0:
+        raise FmxError(f"fmx_xdr_signal_line failed ({rc})")
     return buf.value.decode()
 
 

@@ -47,14 +47,16 @@
 extern "C" {
 #endif
 
-/* ABI history: 12 adds the one-call band receiver (fmx_wb_process_block: one wide IQ capture in, every
+/* ABI history: 13 adds the band receiver's RF level (fmx_wb_signal, fmx_wb_set_signal_params,
+ * fmx_wb_signal_reset: every station's level from the rows of the call just queued) and fmx_xdr_signal_line;
+ * 12 adds the one-call band receiver (fmx_wb_process_block: one wide IQ capture in, every
  * station's audio, stereo state and RDS groups out), FMX_DIAG_FE_GENERIC and fmx_diag_lds_bytes; 11 adds the band scan (fmx_wb_scan_*, fmx_scan_peaks: one wide IQ capture in, the RF
  * level of every scan point out); 10 adds the wideband channelizer (fmx_wb_*: one wide IQ capture in, every tuned
  * channel's baseband out); 9 (round 6) adds fmx_diag_set / fmx_diag_rds_ring and fmx_build_info; 8 (round 5) adds FMX_K_BITS (FMX_K_COUNT 8); 7 (round 5) adds fmx_host_stats and FMX_K_FRONTEND_GENERIC (FMX_K_COUNT 7); 6 (round 4) adds FMX_K_PILOT (FMX_K_COUNT 6); 5 (round 4) added FMX_K_RS (FMX_K_COUNT 5; fmx_kernel_times
  * fills at most n entries); 4 (round 3) added fmx_synth_config.level_spread_db,
  * which changed that struct's size: callers must be rebuilt against this
  * header. */
-#define FMX_ABI_VERSION 12
+#define FMX_ABI_VERSION 13
 
 enum {
   FMX_OK = 0,
@@ -261,9 +263,8 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
  * stereo and RDS as the handle's config says.  d_clip_ratio is
  * FMDemod::getClippingRatio of processSplitComplex on the rows (the share of
  * the call's n samples with |re| or |im| >= 0.995).  d_signal must be NULL
- * (FMX_E_INVALID otherwise): the RF level of a station in a shared capture is
- * the band scan's definition above, and a scan object with its points at the
- * station frequencies delivers it from the same capture.
+ * (FMX_E_INVALID otherwise): fmx_wb_signal below, called behind this call,
+ * delivers every station's RF level from this call's own rows.
  * Conditions: the handle has iq_rate == dsp_rate, the channelizer that
  * dsp_rate and the handle's channel count (FMX_E_INVALID otherwise, the
  * message names this function); n <= min(the handle's block, the
@@ -277,6 +278,51 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
  * with n % 4 == 0 run the fast front end (k_fecf, then k_pilot / k_rs as after
  * k_fe8); every other n >= 1 is correct on the generic one. */
 int fmx_wb_process_block(void *wb, const void *d_wide, int n, const fmx_block_out *out);
+/* The RF level of every channel from the rows of the object's most recent
+ * non-empty call (fmx_wb_process or fmx_wb_process_block; a call of n == 0
+ * does nothing and does not count): what the reference computes on every read
+ * (main.cpp:1166-1174) and hands to XDRServer::updateSignal every block
+ * (main.cpp:1301).  The definition is the band scan's (below), taken over the
+ * rows the channelizer produced: with y_c[m], m = 0 .. n - 1, channel c's row
+ * of that call, history and sample counter included as fmx_wb_process defines
+ * them,
+ *   P_c  = (1 / n) sum_m |y_c[m]|^2
+ *   rms  = sqrt(max(1e-15, 0.5 P_c)),  dbfs = 20 log10(rms + 1e-12)
+ * and compensated_dbfs, level120 (one float conversion), level120_smoothed
+ * (one smoother per channel of the object), hard_clip_ratio and
+ * near_clip_ratio (of the call's n * D raw samples, the same in every record)
+ * as the scan forms them; no mean is removed, for the scan's reason.  What
+ * differs from the scan: every one of the n outputs counts -- the object has
+ * the history, so no window reaches before known samples; the first
+ * taps_per_phase outputs after fmx_wb_reset are the filter filling from zeros
+ * and count as they are; every n >= 1 is valid.
+ * d_level is [n_channels], 8-byte aligned; cells outside [0, n_channels) are
+ * never written.  The call is queued on the handle's stage stream behind the
+ * call it measures and ahead of the object's next call; it neither joins nor
+ * drains the other streams, so fmx_wb_process_block calls stay queued ahead.
+ * Results are valid after fmx_sync; d_level may rotate with the caller's
+ * output sets.  The object remembers the measured call's d_wide, n, rows and
+ * stride: after fmx_wb_process the rows are the caller's d_out, and d_out
+ * and d_wide must stay as they were until this call's work is done (after
+ * fmx_wb_process_block: d_wide).  Any geometry fmx_wb_process accepts is read
+ * correctly (4-byte aligned rows, any out_stride >= n_out), and the sum's
+ * order depends on n alone: equal rows give equal records, bit for bit.
+ * A call is measured once: FMX_E_INVALID (the message names this function)
+ * when no call has been made since creation, when the most recent call has
+ * been measured already (the smoother would advance twice), for a NULL d_level
+ * and for one that is not 8-byte aligned. */
+int fmx_wb_signal(void *wb, fmx_signal_level *d_level);
+/* One set per object (the capture has one tuner gain); defaults as
+ * fmx_set_signal_params' (gain 0, factor 0.5, bias -4, floor -55, ceil -19).
+ * The values travel with each launch: a change holds from the next
+ * fmx_wb_signal on. */
+int fmx_wb_set_signal_params(void *wb, int applied_gain_db, double gain_comp_factor, double bias_db,
+                             double floor_dbfs, double ceil_dbfs);
+/* Restarts channel's level smoother (-1: every channel's), ordered behind the
+ * level calls queued so far.  fmx_wb_reset and fmx_wb_set_freq leave the
+ * smoothers alone: the reference's rfLevelSmoother (main.cpp:698) lives
+ * across retunes. */
+int fmx_wb_signal_reset(void *wb, int channel);
 /* host only: the channel weights W[k] = 2 fc h[k] exp(+j 2 pi f k / wide_rate),
  * k = 0..L-1, as 2L floats (re, im) read back from the kernel's f16 hi + lo
  * tables.  Returns 2L (negative on error). */
@@ -452,6 +498,14 @@ int fmx_xdr_rds_lines(fmx_xdr_pi_state *s, const fmx_rds_group *groups, int n, c
  * decimal; points with reads == 0 skipped; empty when no point).  level_sum
  * holds summed fmx_signal_level.level120 values.  Same return convention. */
 int fmx_xdr_scan_line(const int *freq_khz, const double *level_sum, const int *reads, int n, char *out, int cap);
+/* XDRServer::updateSignal + buildSignalLine (xdr_server.cpp:368-397): the
+ * level line of one station, "S" mode "%.1f" "," cci "," aci "\n" of
+ * deci / 10.0 with deci = (int)round(clamp(level, 0, 120) * 10) in float (a
+ * NaN level counts as 0); mode is m (mono), s (stereo), M (forced mono) or S
+ * (forced mono while stereo is detected).  level: a record's
+ * level120_smoothed; stereo: d_stereo_indicator; the reference sends -1 for
+ * cci and aci.  NUL-terminated; fmx_xdr_rds_lines' return convention. */
+int fmx_xdr_signal_line(float level, int stereo, int forced_mono, int cci, int aci, char *out, int cap);
 /* AudioOutput::writeWAVHeader (audio_output.cpp:1346-1377): 44 bytes for
  * data_bytes of S16LE 32 kHz stereo.  Returns 44. */
 int fmx_wav_header(uint32_t data_bytes, uint8_t *out44);

@@ -23,7 +23,19 @@ signal), stereo + RDS -- and a slice: D = 10 (2.4 MS/s), 5 channels.
 Writes one JSON document (default profiles/wb_receiver.json) and exits
 non-zero when, in the band case, A's median is not below C's or A is not
 faster than real time.  The slice is reported, not gated: five channels are
-launch latency.  Needs a GPU."""
+launch latency.
+
+--signal times a fourth arm instead of B, alternating with A and C in the same
+scheme --
+
+  A+S  arm A's call followed by fmx_wb_signal (k_wb_scan_clip and k_wb_level
+       behind the call's front end on the stage stream): every station's RF
+       level with its audio, three rotating record arrays;
+
+writes profiles/wb_receiver_signal.json by default and exits non-zero when, in
+the band case, the A+S median is not below C's or A+S is not faster than real
+time.  The A+S / A ratio is reported with both arms' min-max, not gated.
+Needs a GPU."""
 import argparse
 import json
 import os
@@ -45,7 +57,7 @@ def _stats(ms):
     return dict(median=float(np.median(ms)), min=float(ms[0]), max=float(ms[-1]))
 
 
-def run_case(fmx, torch, name, D, channels, step, warmup, reps, train):
+def run_case(fmx, torch, name, D, channels, step, warmup, reps, train, signal=False):
     Fs, C, n = D * DSP, channels, N_OUT
     freqs = [-int((C - 1) * step / 2) + i * step for i in range(C)]
     h = fmx.Handle(fmx.make_config(iq_rate=DSP, dsp_rate=DSP, block=n), C)
@@ -65,12 +77,18 @@ def run_case(fmx, torch, name, D, channels, step, warmup, reps, train):
     # the stage chain's buffers
     bb, mpx, lf, rf, sl, sr = f(C, 2 * n), f(C, n), f(C, n), f(C, n), f(C, n), f(C, n)
     s_st, s_pil, s_cnt, s_gcnt, s_grp = z(C), z(C), z(C), z(C), z(C, GS, 4)
+    lev = torch.zeros((3, C * 40), dtype=torch.uint8, device=dev)  # fmx_signal_level records, rotating with the sets
     torch.cuda.synchronize()
     calls = [0]
 
     def one_call():
         wb.process_block(raw.data_ptr(), n, outs[calls[0] % 3])
         calls[0] += 1
+
+    def one_call_and_signal():
+        k = calls[0] % 3
+        one_call()
+        wb.signal(lev[k].data_ptr())
 
     def stage_chain():
         wb.process(raw.data_ptr(), n, bb.data_ptr(), n)
@@ -80,6 +98,9 @@ def run_case(fmx, torch, name, D, channels, step, warmup, reps, train):
         h.rds(mpx.data_ptr(), n, n, s_grp.data_ptr(), GS, s_gcnt.data_ptr())
 
     arms = {"A_one_call": (0, one_call), "B_one_call_generic_front_end": (1, one_call), "C_stage_calls": (0, stage_chain)}
+    if signal:
+        arms = {"A_one_call": (0, one_call), "AS_one_call_and_signal": (0, one_call_and_signal),
+                "C_stage_calls": (0, stage_chain)}
 
     def run_train(generic, fn, k):
         h.diag_set(fmx.FMX_DIAG_FE_GENERIC, generic)
@@ -103,6 +124,11 @@ def run_case(fmx, torch, name, D, channels, step, warmup, reps, train):
     h.timing_enable(False)
     assert bool(torch.isfinite(T["pl"]).all()) and bool(torch.isfinite(sl).all())
     assert int(T["cnt"].min()) > 0 and int(s_cnt.min()) > 0
+    if signal:
+        import numpy as np
+        rec = lev.cpu().numpy().view(np.dtype([("level120", "<f4"), ("smoothed", "<f4"), ("dbfs", "<f8"), ("cdb", "<f8"),
+                                               ("hard", "<f8"), ("near", "<f8")]))
+        assert np.isfinite(rec["dbfs"]).all() and (rec["dbfs"] > -100.0).all() and (rec["hard"] > 0.0).all()
     wb.close()
     h.close()
     signal_ms = n / DSP * 1e3
@@ -112,8 +138,14 @@ def run_case(fmx, torch, name, D, channels, step, warmup, reps, train):
         st = _stats(ms[k])
         res[k] = dict(ms_per_call=st, times_real_time=signal_ms / st["median"])
     res["A_over_C"] = res["A_one_call"]["ms_per_call"]["median"] / res["C_stage_calls"]["ms_per_call"]["median"]
-    res["A_over_B"] = (res["A_one_call"]["ms_per_call"]["median"] /
-                       res["B_one_call_generic_front_end"]["ms_per_call"]["median"])
+    if signal:
+        res["AS_over_A"] = (res["AS_one_call_and_signal"]["ms_per_call"]["median"] /
+                            res["A_one_call"]["ms_per_call"]["median"])
+        res["AS_over_C"] = (res["AS_one_call_and_signal"]["ms_per_call"]["median"] /
+                            res["C_stage_calls"]["ms_per_call"]["median"])
+    else:
+        res["A_over_B"] = (res["A_one_call"]["ms_per_call"]["median"] /
+                           res["B_one_call_generic_front_end"]["ms_per_call"]["median"])
     res["kernel_ms_per_launch_arm_A"] = {k: (v[0] / v[1] if v[1] else None) for k, v in kt.items()}
     res["kernel_launches_arm_A"] = {k: v[1] for k, v in kt.items()}
     return res
@@ -124,16 +156,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--train", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wb_receiver.json"))
+    ap.add_argument("--signal", action="store_true", help="time arm A+S (the call followed by fmx_wb_signal) instead of B")
+    ap.add_argument("--out", default=None, help="default profiles/wb_receiver.json (wb_receiver_signal.json with --signal)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "wb_receiver_signal.json" if a.signal else "wb_receiver.json")
     if a.reps < 10:
         ap.error("--reps must be at least 10")
     import torch
     import fmx
     if not torch.cuda.is_available():
         sys.exit("bench_band_receiver: no GPU")
-    cases = [run_case(fmx, torch, "band_24MSps_205ch_100kHz", 100, 205, 100_000, a.warmup, a.reps, a.train),
-             run_case(fmx, torch, "slice_2.4MSps_5ch", 10, 5, 400_000, a.warmup, a.reps, a.train)]
+    cases = [run_case(fmx, torch, "band_24MSps_205ch_100kHz", 100, 205, 100_000, a.warmup, a.reps, a.train, a.signal),
+             run_case(fmx, torch, "slice_2.4MSps_5ch", 10, 5, 400_000, a.warmup, a.reps, a.train, a.signal)]
     doc = dict(tool="tools/bench_band_receiver.py", library=fmx.build_info(), device=torch.cuda.get_device_name(0),
                cases=cases)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -146,6 +181,11 @@ def main():
         sys.exit("bench_band_receiver: the one call is not faster than the five stage calls in the band case")
     if band["A_one_call"]["times_real_time"] <= 1.0:
         sys.exit("bench_band_receiver: the band case is slower than real time")
+    if a.signal:
+        if band["AS_over_C"] >= 1.0:
+            sys.exit("bench_band_receiver: the call with fmx_wb_signal is not faster than the five stage calls in the band case")
+        if band["AS_one_call_and_signal"]["times_real_time"] <= 1.0:
+            sys.exit("bench_band_receiver: the band case with fmx_wb_signal is slower than real time")
 
 
 if __name__ == "__main__":

@@ -2256,6 +2256,408 @@ int fmx_wb_signal_reset(void *wb, int channel) {
   return FMX_OK;
 }
 
+/* ---- capture bank (fmx.h; kernels in fmx_wb_bank.inc) ---- */
+namespace {
+struct WbBank {
+  Handle *h = nullptr;
+  WbPlan p;
+  int S = 0, C = 0, G = 0;    // captures, channels of all captures, groups
+  std::vector<int> first;     // [S + 1]
+  uint16_t *d_w = nullptr;    // [C][4][Lp] weight rows
+  uint32_t *d_fpos = nullptr; // [C] f mod Fs
+  int *d_groups = nullptr;    // [G][3] k_wbb's work list
+  int *d_chan_cap = nullptr;  // [C] the capture of a channel
+  void *d_hist[2] = {};       // [S][L - 1] raw samples, the buffers taking turns (every capture advances with every call)
+  int cur = 0;
+  WbbState *d_state = nullptr; // [S] counter and history fill: read and advanced on the device
+  double *d_sp = nullptr;      // [S][4] signal parameters, written by k_wbb_set_params on sA
+  // fmx_wb_bank_set_freq's staging image, as Wb's
+  uint16_t *stage = nullptr;
+  hipEvent_t ev = nullptr;
+  bool ev_set = false;
+  float *d_rows = nullptr; // fmx_wb_bank_process_block's rows [C][rows_stride], as Wb's
+  int rows_stride = 0;
+  // fmx_wb_bank_signal: the most recent non-empty call
+  const void *sig_wide = nullptr;
+  size_t sig_wstride = 0;
+  const float *sig_rows = nullptr;
+  int sig_stride = 0, sig_n = 0;
+  bool sig_pending = false;
+  uint32_t *d_clip = nullptr; // [S][clip workgroups of a full block][2] (allocated on first use)
+  float *d_sm = nullptr;      // [C][2] level smoothers
+};
+WbBank *WBK(void *p) { return static_cast<WbBank *>(p); }
+void wbb_free(WbBank *b) {
+  if (b->d_w) hipFree(b->d_w);
+  if (b->d_fpos) hipFree(b->d_fpos);
+  if (b->d_groups) hipFree(b->d_groups);
+  if (b->d_chan_cap) hipFree(b->d_chan_cap);
+  for (void *x : b->d_hist)
+    if (x) hipFree(x);
+  if (b->d_state) hipFree(b->d_state);
+  if (b->d_sp) hipFree(b->d_sp);
+  if (b->stage) hipHostFree(b->stage);
+  if (b->ev) hipEventDestroy(b->ev);
+  if (b->d_rows) hipFree(b->d_rows);
+  if (b->d_clip) hipFree(b->d_clip);
+  if (b->d_sm) hipFree(b->d_sm);
+  delete b;
+}
+
+// k_wbb and k_wbb_hist of one call on sA; the captures' state advances on the device
+int wbb_run(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float *d_out, int out_stride, const char *who) {
+  Handle *h = b->h;
+  const WbPlan &p = b->p;
+  WbbArgs a{};
+  a.in = d_wide;
+  a.wide_stride = wide_stride;
+  a.s16 = p.format == FMX_WB_S16;
+  a.D = p.D;
+  a.L = p.L;
+  a.Lp = p.Lp;
+  a.n_out = n_out;
+  a.C = b->C;
+  a.S = b->S;
+  a.w = b->d_w;
+  a.fpos = b->d_fpos;
+  a.hist = b->d_hist[b->cur];
+  a.hist_out = b->d_hist[b->cur ^ 1];
+  a.state = b->d_state;
+  a.groups = b->d_groups;
+  a.G = b->G;
+  a.fs = static_cast<uint32_t>(p.fs);
+  a.inv_fs = 1.0 / static_cast<double>(p.fs);
+  a.scale = static_cast<float>(std::ldexp(a.s16 ? 1.0 / 32768.0 : 1.0 / 255.0, -p.sexp));
+  a.out = d_out;
+  a.out_stride = out_stride;
+  int rc;
+  if ((rc = launch_wbb(a, h->sA)) != FMX_OK) {
+    h->err = std::string(who) + ": kernel launch failed";
+    return rc;
+  }
+  b->cur ^= 1;
+  b->sig_wide = d_wide;
+  b->sig_wstride = wide_stride;
+  b->sig_rows = d_out;
+  b->sig_stride = out_stride;
+  b->sig_n = n_out;
+  b->sig_pending = true;
+  return FMX_OK;
+}
+} // namespace
+
+int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, const int *first_channel,
+                       const int *freq_hz, void **bank) {
+  Handle *h = H(handle);
+  if (bank) *bank = nullptr;
+  if (!h) return FMX_E_INVALID;
+  if (!cfg || !first_channel || !bank) {
+    h->err = "fmx_wb_bank_create: null argument";
+    return FMX_E_INVALID;
+  }
+  if (n_captures < 1 || n_captures > FMX_WBB_CAPTURES_MAX) {
+    h->err = "fmx_wb_bank_create: n_captures must be 1..1024";
+    return FMX_E_INVALID;
+  }
+  bool ok = first_channel[0] == 0;
+  for (int s = 0; ok && s < n_captures; ++s) ok = first_channel[s + 1] >= first_channel[s];
+  const int Cn = ok ? first_channel[n_captures] : 0;
+  if (!ok || (Cn > 0 && !freq_hz)) {
+    h->err = "fmx_wb_bank_create: first_channel must start at 0 and not decrease; freq_hz is required";
+    return FMX_E_INVALID;
+  }
+  WbPlan p;
+  int rc = wb_plan(*cfg, &p, &h->err);
+  if (rc != FMX_OK) return rc;
+  for (int c = 0; c < Cn; ++c)
+    if (!wb_freq_ok(p, freq_hz[c])) {
+      h->err = "fmx_wb_bank_create: channel " + std::to_string(c) + " lies outside +- wide_rate / 2";
+      return FMX_E_INVALID;
+    }
+  std::vector<int> groups(static_cast<size_t>(3) * (static_cast<size_t>(n_captures) + Cn / 16 + 1));
+  const int G = wbb_groups(first_channel, n_captures, groups.data(), static_cast<int>(groups.size() / 3));
+  if (G < 0) {
+    h->err = "fmx_wb_bank_create: more than 65535 groups of 16 channels";
+    return G == FMX_E_CAPACITY ? FMX_E_CAPACITY : FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  WbBank *b = new (std::nothrow) WbBank();
+  if (!b) return FMX_E_NOMEM;
+  b->h = h;
+  b->p = p;
+  b->S = n_captures;
+  b->C = Cn;
+  b->G = G;
+  b->first.assign(first_channel, first_channel + n_captures + 1);
+  const size_t row = static_cast<size_t>(4) * p.Lp;
+  const size_t hist_bytes = static_cast<size_t>(n_captures) * (p.L - 1) * wb_sample_bytes(p);
+  const size_t cn1 = static_cast<size_t>(std::max(Cn, 1)), g1 = static_cast<size_t>(std::max(G, 1));
+  std::vector<uint16_t> rows(row * cn1);
+  std::vector<uint32_t> fpos(cn1);
+  std::vector<int> chan_cap(cn1);
+  for (int s = 0; s < n_captures; ++s)
+    for (int c = first_channel[s]; c < first_channel[s + 1]; ++c) {
+      wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
+      fpos[c] = wb_freq_mod(p, freq_hz[c]);
+      chan_cap[c] = s;
+    }
+  std::vector<WbbState> state(n_captures); // counter 0, nothing valid
+  std::vector<double> sp(static_cast<size_t>(4) * n_captures);
+  for (int s = 0; s < n_captures; ++s) {
+    const double def[4] = {0.0, -4.0, -55.0, -19.0}; // gain*factor, bias, floor, ceil
+    std::memset(&state[s], 0, sizeof(WbbState));
+    for (int k = 0; k < 4; ++k) sp[4 * s + k] = def[k];
+  }
+  const size_t sm_bytes = cn1 * 2 * sizeof(float);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_w), rows.size() * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_fpos), fpos.size() * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_groups), g1 * 3 * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_chan_cap), cn1 * sizeof(int));
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc(&b->d_hist[k], hist_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_state), state.size() * sizeof(WbbState));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_sp), sp.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_sm), sm_bytes);
+  if (e != hipSuccess) {
+    h->err = std::string("fmx_wb_bank_create: hipMalloc failed: ") + hipGetErrorString(e);
+    wbb_free(b);
+    return FMX_E_NOMEM;
+  }
+  e = hipHostMalloc(reinterpret_cast<void **>(&b->stage), row * sizeof(uint16_t) + sizeof(uint32_t), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev, hipEventDisableTiming);
+  // synchronous copies: the tables are complete before the first call is queued
+  if (e == hipSuccess) e = hipMemcpy(b->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_fpos, fpos.data(), fpos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess && G > 0)
+    e = hipMemcpy(b->d_groups, groups.data(), static_cast<size_t>(G) * 3 * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_chan_cap, chan_cap.data(), chan_cap.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_state, state.data(), state.size() * sizeof(WbbState), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_sp, sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice);
+  // the smoothers' only readers run on sA: cleared there, ahead of the first of them
+  if (e == hipSuccess) e = hipMemsetAsync(b->d_sm, 0, sm_bytes, h->sA);
+  if (e != hipSuccess) {
+    h->err = std::string("fmx_wb_bank_create: ") + hipGetErrorString(e);
+    wbb_free(b);
+    return FMX_E_HIP;
+  }
+  *bank = b;
+  return FMX_OK;
+}
+
+int fmx_wb_bank_destroy(void *bank) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  if (b->h->sA) hipStreamSynchronize(b->h->sA);
+  wbb_free(b);
+  return FMX_OK;
+}
+
+int fmx_wb_bank_set_freq(void *bank, int channel, int freq_hz) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (channel < 0 || channel >= b->C || !wb_freq_ok(b->p, freq_hz)) {
+    h->err = "fmx_wb_bank_set_freq: channel or frequency out of range";
+    return FMX_E_INVALID;
+  }
+  if (b->ev_set) HIP_TRY(hipEventSynchronize(b->ev)); // the staging image's last copy has left it
+  const size_t row = static_cast<size_t>(4) * b->p.Lp;
+  wb_weight_rows(b->p, freq_hz, b->stage);
+  const uint32_t fm = wb_freq_mod(b->p, freq_hz);
+  std::memcpy(b->stage + row, &fm, sizeof(fm));
+  // on the stage stream: after the calls queued so far, before later ones
+  HIP_TRY(hipMemcpyAsync(b->d_w + row * channel, b->stage, row * sizeof(uint16_t), hipMemcpyHostToDevice, h->sA));
+  HIP_TRY(hipMemcpyAsync(b->d_fpos + channel, b->stage + row, sizeof(uint32_t), hipMemcpyHostToDevice, h->sA));
+  HIP_TRY(hipEventRecord(b->ev, h->sA));
+  b->ev_set = true;
+  return FMX_OK;
+}
+
+int fmx_wb_bank_reset(void *bank, int capture, int64_t sample0) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (capture < -1 || capture >= b->S || sample0 < 0) {
+    h->err = "fmx_wb_bank_reset: capture out of range or negative sample index";
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // a one-thread kernel on sA: behind the calls queued so far, ahead of later ones
+  int rc;
+  if ((rc = launch_wbb_set_state(b->d_state, b->S, capture, static_cast<uint64_t>(sample0), h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_bank_reset: kernel launch failed";
+    return rc;
+  }
+  return FMX_OK;
+}
+
+int fmx_wb_bank_process(void *bank, const void *d_wide, size_t wide_stride, int n_out, float *d_out, int out_stride) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  const WbPlan &p = b->p;
+  if (n_out < 0 || (n_out > 0 && (!d_wide || (b->C > 0 && !d_out) || out_stride < n_out))) {
+    h->err = "fmx_wb_bank_process: null buffer, negative n_out or out_stride < n_out";
+    return FMX_E_INVALID;
+  }
+  if (n_out > p.block) {
+    h->err = "fmx_wb_bank_process: n_out exceeds the object's block";
+    return FMX_E_CAPACITY;
+  }
+  if (wide_stride < static_cast<size_t>(n_out) * static_cast<size_t>(p.D)) {
+    h->err = "fmx_wb_bank_process: wide_stride is less than n_out * D samples";
+    return FMX_E_INVALID;
+  }
+  if (n_out == 0) return FMX_OK;
+  int rc;
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  return wbb_run(b, d_wide, wide_stride, n_out, d_out, out_stride, "fmx_wb_bank_process");
+}
+
+int fmx_wb_bank_process_block(void *bank, const void *d_wide, size_t wide_stride, int n, const fmx_block_out *o) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  const WbPlan &p = b->p;
+  const char *bad = nullptr;
+  if (h->M != 1) bad = "the handle's iq_rate must equal its dsp_rate";
+  else if (p.fs / p.D != h->cfg.dsp_rate) bad = "the bank's dsp_rate is not the handle's";
+  else if (b->C != h->C) bad = "the bank's channel total is not the handle's channel count";
+  else if (n < 0 || (n > 0 && !d_wide)) bad = "null input or negative n";
+  else if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count) bad = "d_pcm_l, d_pcm_r and d_pcm_count are required";
+  else if (o->d_signal) bad = "d_signal must be NULL (fmx_wb_bank_signal, called behind this call, delivers every station's RF level)";
+  else if (n > 0 && wide_stride < static_cast<size_t>(n) * static_cast<size_t>(p.D)) bad = "wide_stride is less than n * D samples";
+  if (bad) {
+    h->err = std::string("fmx_wb_bank_process_block: ") + bad;
+    return FMX_E_INVALID;
+  }
+  if (n > std::min(h->cfg.block, p.block)) {
+    h->err = "fmx_wb_bank_process_block: n exceeds the handle's or the bank's block";
+    return FMX_E_CAPACITY;
+  }
+  if (n == 0) return FMX_OK;
+  int rc;
+  if (!b->d_rows) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int stride = (p.block + 1) & ~1;
+    if (hipMalloc(reinterpret_cast<void **>(&b->d_rows), static_cast<size_t>(b->C) * stride * 2 * sizeof(float)) != hipSuccess) {
+      b->d_rows = nullptr;
+      h->err = "fmx_wb_bank_process_block: hipMalloc failed";
+      return FMX_E_NOMEM;
+    }
+    b->rows_stride = stride;
+  }
+  // fmx_wb_process_block's sequence with k_wbb in k_wb's place
+  if ((rc = prepare_pipelined(h)) != FMX_OK) return rc;
+  if (h->timing) harvest_timing(h);
+  if ((rc = wbb_run(b, d_wide, wide_stride, n, b->d_rows, b->rows_stride, "fmx_wb_bank_process_block")) != FMX_OK) return rc;
+  Step s{};
+  s.cf = b->d_rows;
+  s.cf_stride = 2 * b->rows_stride;
+  s.n = n;
+  s.o = o;
+  s.stereo = h->cfg.stereo != 0;
+  s.rds = h->cfg.rds != 0;
+  s.buf = static_cast<int>(h->step % FMX_NBUF);
+  s.mpx = o->d_mpx ? o->d_mpx : h->mpx[s.buf];
+  s.mpx_stride = o->d_mpx ? o->mpx_stride : h->row;
+  s.evFE = h->evF[h->step % FMX_FRING];
+  if ((rc = step_sA(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sC(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sB(h, s)) != FMX_OK) return rc;
+  if ((rc = step_sD(h, s)) != FMX_OK) return rc;
+  h->block_index++;
+  step_done(h, s.stereo);
+  return FMX_OK;
+}
+
+int fmx_wb_bank_signal(void *bank, fmx_signal_level *d_level) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  const WbPlan &p = b->p;
+  const char *bad = nullptr;
+  if (!d_level) bad = "null d_level";
+  else if (reinterpret_cast<uintptr_t>(d_level) & 7) bad = "d_level is not 8-byte aligned";
+  else if (!b->sig_wide) bad = "no fmx_wb_bank_process / fmx_wb_bank_process_block call of n >= 1 to measure yet";
+  else if (!b->sig_pending) bad = "the most recent call has been measured (one level per call: a smoother advances once)";
+  if (bad) {
+    h->err = std::string("fmx_wb_bank_signal: ") + bad;
+    return FMX_E_INVALID;
+  }
+  if (b->C == 0) { // nothing to measure
+    b->sig_pending = false;
+    return FMX_OK;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (!b->d_clip) {
+    const size_t n_clip = static_cast<size_t>(b->S) * wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D) * 2;
+    if (hipMalloc(reinterpret_cast<void **>(&b->d_clip), n_clip * sizeof(uint32_t)) != hipSuccess) {
+      b->d_clip = nullptr;
+      h->err = "fmx_wb_bank_signal: hipMalloc failed";
+      return FMX_E_NOMEM;
+    }
+  }
+  // on sA alone, behind the call it measures: no join, the other streams keep running
+  WbbLevelArgs a{};
+  a.rows = b->sig_rows;
+  a.stride = b->sig_stride;
+  a.n = b->sig_n;
+  a.C = b->C;
+  a.S = b->S;
+  a.in = b->sig_wide;
+  a.wide_stride = b->sig_wstride;
+  a.s16 = p.format == FMX_WB_S16;
+  a.D = p.D;
+  a.clip = b->d_clip;
+  a.chan_cap = b->d_chan_cap;
+  a.sm = b->d_sm;
+  a.level = d_level;
+  a.sp = b->d_sp;
+  int rc;
+  if ((rc = launch_wbb_level(a, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_bank_signal: kernel launch failed";
+    return rc;
+  }
+  b->sig_pending = false;
+  return FMX_OK;
+}
+
+int fmx_wb_bank_set_signal_params(void *bank, int capture, int applied_gain_db, double gain_comp_factor, double bias_db,
+                                  double floor_dbfs, double ceil_dbfs) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (capture < -1 || capture >= b->S) {
+    h->err = "fmx_wb_bank_set_signal_params: capture out of range";
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // computeSignalLevel: compensated = (dbfs - gain * factor) + bias; a one-thread kernel on sA carries the values
+  const double v[4] = {static_cast<double>(applied_gain_db) * gain_comp_factor, bias_db, floor_dbfs, ceil_dbfs};
+  int rc;
+  if ((rc = launch_wbb_set_params(b->d_sp, b->S, capture, v, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_bank_set_signal_params: kernel launch failed";
+    return rc;
+  }
+  return FMX_OK;
+}
+
+int fmx_wb_bank_signal_reset(void *bank, int channel) {
+  WbBank *b = WBK(bank);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (channel < -1 || channel >= b->C) {
+    h->err = "fmx_wb_bank_signal_reset: channel out of range";
+    return FMX_E_INVALID;
+  }
+  // on sA: behind the level calls queued so far, ahead of later ones
+  const size_t one = 2 * sizeof(float);
+  if (channel < 0) {
+    if (b->C > 0) HIP_TRY(hipMemsetAsync(b->d_sm, 0, one * static_cast<size_t>(b->C), h->sA));
+  } else HIP_TRY(hipMemsetAsync(b->d_sm + 2 * static_cast<size_t>(channel), 0, one, h->sA));
+  return FMX_OK;
+}
+
 /* ---- band scan (fmx.h; kernels in fmx_wb_scan.inc) ---- */
 namespace {
 struct WbScan {

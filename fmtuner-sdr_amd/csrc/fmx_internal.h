@@ -361,6 +361,55 @@ struct WbLevelArgs {
 };
 int launch_wb_level(const WbLevelArgs &a, void *stream);
 
+// ---- capture bank (fmx_wb_bank.inc): S captures of one plan channelized by one launch ----
+#define FMX_WBB_CAPTURES_MAX 1024
+#define FMX_WBB_GROUPS_MAX 65535 // the kernel's grid.y
+// one capture's stream position, kept on the device: k_wbb reads it, k_wbb_hist
+// (one writer per capture) advances it, k_wbb_set_state rewrites it
+struct WbbState {
+  uint64_t counter; // wide-sample index of the next call's first sample
+  int valid;        // samples of the capture's history that exist (since its last reset)
+  int pad;
+};
+struct WbbArgs {
+  const void *in;          // [S][wide_stride] wide samples, interleaved I/Q; n_out * D of each row are read
+  size_t wide_stride;      // samples
+  int s16, in_al;          // as WbArgs
+  int D, L, Lp, n_out, C, S; // C: the channels of all captures
+  const uint16_t *w;       // [C][4][Lp] weight rows
+  const uint32_t *fpos;    // [C] f mod Fs
+  const void *hist;        // [S][L - 1] raw samples before this call
+  void *hist_out;          // the same after it (another buffer)
+  WbbState *state;         // [S]
+  const int *groups;       // [G][3] capture, first channel, channels (1..16): fmx_wb_bank_groups
+  int G;
+  uint32_t fs;
+  double inv_fs;
+  float scale;
+  float *out;
+  int out_stride;
+  int nt;                  // set by the launcher
+};
+// the work list of k_wbb (fmx_wb_design.cpp; fmx_wb_bank_groups is its C entry)
+int wbb_groups(const int *first_channel, int n_captures, int *out, int cap);
+int launch_wbb(const WbbArgs &a, void *stream); // k_wbb, then k_wbb_hist (which advances the state)
+int launch_wbb_set_state(WbbState *state, int S, int capture /* -1: all */, uint64_t counter, void *stream);
+int launch_wbb_set_params(double *sp /* [S][4] */, int S, int capture /* -1: all */, const double *v, void *stream);
+struct WbbLevelArgs {
+  const float *rows;       // as WbLevelArgs, C the channels of all captures
+  int stride, n, C, S;
+  const void *in;          // the call's [S][wide_stride] wide samples
+  size_t wide_stride;
+  int s16, D;
+  uint32_t *clip;          // [S][nclip][2]
+  const int *chan_cap;     // [C] the capture a channel belongs to
+  float *sm;               // [C][2]
+  fmx_signal_level *level; // [C]
+  const double *sp;        // [S][4] gain*factor, bias, floor, ceil of each capture (device)
+  int nclip;               // set by the launcher
+};
+int launch_wbb_level(const WbbLevelArgs &a, void *stream);
+
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps
 

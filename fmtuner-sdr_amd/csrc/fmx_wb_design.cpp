@@ -131,7 +131,37 @@ int wb_scan_plan(const fmx_wb_scan_config &cfg, WbPlan *p, std::string *err) {
   return FMX_OK;
 }
 
+// The capture bank's work list (k_wbb): one group
+// {capture, first channel, channels 1..16} per 16 channels of a capture, in
+// channel order, none for an empty capture.  Returns the group count G, or
+// FMX_E_INVALID for a bad table, FMX_E_CAPACITY for one of more than 65 535
+// groups, or -G when out is NULL or cap < G (then nothing is written).
+int wbb_groups(const int *first_channel, int n_captures, int *out, int cap) {
+  if (!first_channel || n_captures < 1 || n_captures > FMX_WBB_CAPTURES_MAX || first_channel[0] != 0) return FMX_E_INVALID;
+  int64_t G = 0;
+  for (int s = 0; s < n_captures; ++s) {
+    const int64_t n = static_cast<int64_t>(first_channel[s + 1]) - first_channel[s];
+    if (n < 0) return FMX_E_INVALID;
+    G += (n + 15) / 16;
+  }
+  if (G > FMX_WBB_GROUPS_MAX) return FMX_E_CAPACITY;
+  if (G > 0 && (!out || cap < G)) return -static_cast<int>(G);
+  int g = 0;
+  for (int s = 0; s < n_captures; ++s)
+    for (int c = first_channel[s]; c < first_channel[s + 1]; c += 16) {
+      out[3 * g] = s;
+      out[3 * g + 1] = c;
+      out[3 * g + 2] = std::min(16, first_channel[s + 1] - c);
+      ++g;
+    }
+  return g;
+}
+
 } // namespace fmx
+
+extern "C" int fmx_wb_bank_groups(const int *first_channel, int n_captures, int *out, int cap) {
+  return fmx::wbb_groups(first_channel, n_captures, out, cap);
+}
 
 extern "C" int fmx_wb_scan_points(const fmx_wb_scan_config *cfg, int *freq_hz, int cap) {
   if (!cfg) return FMX_E_INVALID;

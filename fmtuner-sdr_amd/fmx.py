@@ -119,7 +119,17 @@ def lib():
         "fmx_wb_set_signal_params": (i, [vp, i, C.c_double, C.c_double, C.c_double, C.c_double]),
         "fmx_wb_signal_reset": (i, [vp, i]),
         "fmx_diag_lds_bytes": (i, [i]),
-        "fmx_wb_weights": (i, [C.POINTER(WbConfig), i, fp, i]),
+        "fmx_wb_bank_create": (i, [vp, C.POINTER(WbConfig), i, C.POINTER(i), C.POINTER(i), C.POINTER(vp)]),
+        "fmx_wb_bank_destroy": (i, [vp]),
+        "fmx_wb_bank_set_freq": (i, [vp, i, i]),
+        "fmx_wb_bank_reset": (i, [vp, i, C.c_int64]),
+        "fmx_wb_bank_process": (i, [vp, vp, C.c_size_t, i, vp, i]),
+        "fmx_wb_bank_process_block": (i, [vp, vp, C.c_size_t, i, C.POINTER(BlockOut)]),
+        "fmx_wb_bank_signal": (i, [vp, vp]),
+        "fmx_wb_bank_set_signal_params": (i, [vp, i, i, C.c_double, C.c_double, C.c_double, C.c_double]),
+        "fmx_wb_bank_signal_reset": (i, [vp, i]),
+        "fmx_wb_bank_groups": (i, [C.POINTER(i), i, C.POINTER(i), i]),
+        "fmx_wb_weights": (i,[C.POINTER(WbConfig), i, fp, i]),
         "fmx_wb_scan_create": (i, [vp, C.POINTER(WbScanConfig), C.POINTER(vp)]),
         "fmx_wb_scan_destroy": (i, [vp]),
         "fmx_wb_scan_set_signal_params": (i, [vp, i, C.c_double, C.c_double, C.c_double, C.c_double]),
@@ -381,6 +391,91 @@ class Wideband:
     def signal_reset(self, channel=-1):
         """Restarts one channel's level smoother (-1: every channel's)."""
         self._ck(self.L.fmx_wb_signal_reset(self.w, channel), "fmx_wb_signal_reset")
+
+
+class WidebandBank:
+    """The capture bank of one Handle (fmx_wb_bank_*): len(freq_hz) wide
+    captures of one configuration, capture s with the channels freq_hz[s] (a
+    list, possibly empty), channelized by one launch.  The bank's channels
+    are the captures' in order; d_wide is [captures][wide_stride] samples.
+    Close it before its handle."""
+
+    def __init__(self, handle, wcfg, freq_hz):
+        self.L = lib()
+        self.handle = handle
+        self.cfg = wcfg
+        self.captures = len(freq_hz)
+        self.first = [0]
+        for f in freq_hz:
+            self.first.append(self.first[-1] + len(f))
+        self.n = self.first[-1]
+        flat = [int(v) for f in freq_hz for v in f]
+        first = (C.c_int * (self.captures + 1))(*self.first)
+        f = (C.c_int * max(self.n, 1))(*flat)
+        b = C.c_void_p()
+        rc = self.L.fmx_wb_bank_create(handle.h, C.byref(wcfg), self.captures, first, f, C.byref(b))
+        self.b = b if rc == FMX_OK else None
+        if rc != FMX_OK:
+            raise FmxError(f"fmx_wb_bank_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+
+    def _ck(self, rc, what):
+        if rc != FMX_OK:
+            raise FmxError(f"{what} failed ({rc}): {self.L.fmx_last_error(self.handle.h).decode()}")
+
+    def close(self):
+        if self.b is not None and self.handle.h is not None:
+            self.L.fmx_wb_bank_destroy(self.b)
+        self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_freq(self, channel, freq_hz):
+        self._ck(self.L.fmx_wb_bank_set_freq(self.b, channel, int(freq_hz)), "fmx_wb_bank_set_freq")
+
+    def reset(self, capture=-1, sample0=0):
+        """Restarts one capture's stream (-1: every capture's) at sample0."""
+        self._ck(self.L.fmx_wb_bank_reset(self.b, capture, sample0), "fmx_wb_bank_reset")
+
+    def process(self, d_wide, wide_stride, n_out, d_out, out_stride):
+        """d_wide: [captures][wide_stride] interleaved I/Q samples, n_out * D of
+        each row read; d_out: [n][out_stride] complex float."""
+        self._ck(self.L.fmx_wb_bank_process(self.b, C.c_void_p(d_wide), wide_stride, n_out, C.c_void_p(d_out),
+                                            out_stride), "fmx_wb_bank_process")
+
+    def process_block(self, d_wide, wide_stride, n, out):
+        """fmx_wb_bank_process_block: Wideband.process_block for every capture's stations."""
+        self._ck(self.L.fmx_wb_bank_process_block(self.b, C.c_void_p(d_wide), wide_stride, n, C.byref(out)),
+                 "fmx_wb_bank_process_block")
+
+    def signal(self, d_level):
+        """fmx_wb_bank_signal: Wideband.signal for every channel of the bank."""
+        self._ck(self.L.fmx_wb_bank_signal(self.b, C.c_void_p(d_level)), "fmx_wb_bank_signal")
+
+    def set_signal_params(self, capture=-1, applied_gain_db=0, gain_comp_factor=0.5, bias_db=-4.0, floor_dbfs=-55.0,
+                          ceil_dbfs=-19.0):
+        self._ck(self.L.fmx_wb_bank_set_signal_params(self.b, capture, applied_gain_db, gain_comp_factor, bias_db,
+                                                      floor_dbfs, ceil_dbfs), "fmx_wb_bank_set_signal_params")
+
+    def signal_reset(self, channel=-1):
+        self._ck(self.L.fmx_wb_bank_signal_reset(self.b, channel), "fmx_wb_bank_signal_reset")
+
+
+def wb_bank_groups(first_channel):
+    """fmx_wb_bank_groups: the bank kernel's work list as [(capture, first
+    channel, channels)] for a first_channel table of captures + 1 entries."""
+    first = [int(v) for v in first_channel]
+    n = len(first) - 1
+    cap = max(n, 0) + (max(first[-1], 0) // 16 if first else 0) + 1
+    t = (C.c_int * max(len(first), 1))(*first)
+    out = (C.c_int * (3 * cap))()
+    g = lib().fmx_wb_bank_groups(t, n, out, cap)
+    if g < 0:
+        raise FmxError(f"fmx_wb_bank_groups failed ({g})")
+    return [tuple(out[3 * k:3 * k + 3]) for k in range(g)]
 
 
 def wb_weights(wcfg, freq_hz):

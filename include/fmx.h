@@ -47,7 +47,10 @@
 extern "C" {
 #endif
 
-/* ABI history: 13 adds the band receiver's RF level (fmx_wb_signal, fmx_wb_set_signal_params,
+/* ABI history: the capture bank (fmx_wb_bank_*: many wide captures channelized in one call) arrived at 13
+ * without a bump: its symbols are additions, no existing symbol, struct or enum changed, and a caller built
+ * against the earlier 13 runs unchanged (a caller that needs the bank looks its symbols up);
+ * 13 adds the band receiver's RF level (fmx_wb_signal, fmx_wb_set_signal_params,
  * fmx_wb_signal_reset: every station's level from the rows of the call just queued) and fmx_xdr_signal_line;
  * 12 adds the one-call band receiver (fmx_wb_process_block: one wide IQ capture in, every
  * station's audio, stereo state and RDS groups out), FMX_DIAG_FE_GENERIC and fmx_diag_lds_bytes; 11 adds the band scan (fmx_wb_scan_*, fmx_scan_peaks: one wide IQ capture in, the RF
@@ -327,6 +330,55 @@ int fmx_wb_signal_reset(void *wb, int channel);
  * k = 0..L-1, as 2L floats (re, im) read back from the kernel's f16 hi + lo
  * tables.  Returns 2L (negative on error). */
 int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap);
+
+/* ---- capture bank: many wide captures of one format and rate channelized in one call ----
+ * A bank holds n_captures captures of one fmx_wb_config (1..1024).  Capture s
+ * owns the bank's channels [first_channel[s], first_channel[s + 1]) --
+ * first_channel[0] is 0, the table does not decrease, an empty capture is
+ * legal -- and is fed row s of d_wide, laid out [n_captures][wide_stride]
+ * wide samples (wide_stride >= n * D; samples past n * D of a row are never
+ * read; the base needs the element's alignment only, an unaligned base takes
+ * element loads and gives identical rows).  Each capture behaves as an fmx_wb
+ * object created with the same configuration and the frequencies
+ * freq_hz[first_channel[s] .. first_channel[s + 1]) and fed that row: output
+ * rows, histories, 64-bit sample counters, the ordering of set_freq on the
+ * stage stream, n == 0, the "measured once" rule of the level call and the
+ * error codes all carry over, and the rows are bit for bit the single
+ * object's.  One kernel launch channelizes every capture (DESIGN.md section
+ * 22); the captures' counters and history fill live on the device, so calls,
+ * resets and parameter changes stay queued without host synchronisation.
+ * Per capture: the reset (dongles restart independently; the other captures'
+ * outputs stay bit-identical), the signal parameters (every tuner has its own
+ * gain) and the clip ratios of the level records (those of that capture's
+ * n * D raw samples).  Smoothers are per channel.
+ * fmx_wb_bank_process_block is fmx_wb_process_block with the bank in the
+ * channelizer's place: the same conditions (the bank's channel total is the
+ * handle's), the same step behind it; fmx_wb_bank_signal is fmx_wb_signal.
+ * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
+int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures,
+                       const int *first_channel /* [n_captures + 1] */,
+                       const int *freq_hz /* [first_channel[n_captures]] */, void **bank);
+int fmx_wb_bank_destroy(void *bank);
+int fmx_wb_bank_set_freq(void *bank, int channel, int freq_hz);
+/* capture's stream restarts at wide-sample index sample0 (-1: every capture's),
+ * ordered on the stage stream between the calls queued before and after it */
+int fmx_wb_bank_reset(void *bank, int capture, int64_t sample0);
+int fmx_wb_bank_process(void *bank, const void *d_wide, size_t wide_stride /* samples */, int n_out, float *d_out,
+                        int out_stride);
+int fmx_wb_bank_process_block(void *bank, const void *d_wide, size_t wide_stride, int n, const fmx_block_out *out);
+int fmx_wb_bank_signal(void *bank, fmx_signal_level *d_level);
+/* capture's set (-1: every capture's), ordered on the stage stream: it holds
+ * for the level calls queued after it */
+int fmx_wb_bank_set_signal_params(void *bank, int capture, int applied_gain_db, double gain_comp_factor,
+                                  double bias_db, double floor_dbfs, double ceil_dbfs);
+int fmx_wb_bank_signal_reset(void *bank, int channel /* -1: all */);
+/* host only, no GPU needed: the channelizer kernel's work list, one group
+ * {capture, first channel, channels 1..16} per 16 channels of a capture and
+ * none for an empty capture, as out[G][3].  cap counts groups.  Returns G;
+ * FMX_E_INVALID for a bad table or n_captures outside 1..1024, FMX_E_CAPACITY
+ * for more than 65 535 groups; -G, with nothing written, when cap < G or out
+ * is NULL (n_captures + first_channel[n_captures] / 16 groups always do). */
+int fmx_wb_bank_groups(const int *first_channel, int n_captures, int *out, int cap);
 
 /* ---- band scan: the RF level of every scan point from one wide capture ----
  * The reference's scan (main.cpp:1064-1121: retune, three reads,

@@ -1919,10 +1919,15 @@ namespace {
 struct Wb {
   Handle *h = nullptr;
   WbPlan p;
+  // fmx_wb_create_rational at Q > 1: the plan is rp,
+  // the rows are [C][Q][4][Lp], the history holds rp.Lh - 1 samples and a call
+  // of n outputs consumes n P / Q; p carries fs, format, block, sexp and Lp
+  bool rational = false;
+  WbrPlan rp;
   int C = 0;
-  uint16_t *d_w = nullptr;    // [C][4][Lp] weight rows
+  uint16_t *d_w = nullptr;    // [C][4][Lp] weight rows ([C][Q][4][Lp] on a rational object)
   uint32_t *d_fpos = nullptr; // [C] f mod Fs
-  void *d_hist[2] = {};       // the last L - 1 raw samples, the buffers taking turns
+  void *d_hist[2] = {};       // the last L - 1 (rp.Lh - 1) raw samples, the buffers taking turns
   int cur = 0;                // the buffer holding them
   int valid = 0;              // how many exist since the last reset
   uint64_t counter = 0;       // wide-sample index of the next call's first sample
@@ -1952,6 +1957,10 @@ struct Wb {
 };
 Wb *W(void *p) { return static_cast<Wb *>(p); }
 size_t wb_sample_bytes(const WbPlan &p) { return p.format == FMX_WB_S16 ? 4 : 2; }
+// wide samples a call of n outputs consumes (n a multiple of Q on a rational object)
+int64_t wb_consumed(const Wb *w, int n) {
+  return w->rational ? static_cast<int64_t>(n) / w->rp.Q * w->rp.P : static_cast<int64_t>(n) * w->p.D;
+}
 void wb_free(Wb *w) {
   if (w->d_w) hipFree(w->d_w);
   if (w->d_fpos) hipFree(w->d_fpos);
@@ -1965,6 +1974,58 @@ void wb_free(Wb *w) {
   delete w;
 }
 int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, const char *who);
+
+// The rest of fmx_wb_create / fmx_wb_create_rational once w's plan is set:
+// the channels' weight rows and f mod Fs, the device buffers, the staging
+// image.  Takes w over: on an error it is freed and *wb stays NULL.
+int wb_create_finish(Wb *w, const int *freq_hz, const char *who, void **wb) {
+  Handle *h = w->h;
+  const WbPlan &p = w->p;
+  for (int c = 0; c < w->C; ++c)
+    if (!wb_freq_ok(p, freq_hz[c])) {
+      h->err = std::string(who) + ": channel " + std::to_string(c) + " lies outside +- wide_rate / 2";
+      delete w;
+      return FMX_E_INVALID;
+    }
+  if (hipSetDevice(h->device) != hipSuccess) {
+    h->err = std::string(who) + ": hipSetDevice failed";
+    delete w;
+    return FMX_E_HIP;
+  }
+  const size_t row = static_cast<size_t>(4) * p.Lp * (w->rational ? w->rp.Q : 1);
+  const size_t hist_bytes = static_cast<size_t>(w->rational ? w->rp.Lh - 1 : p.L - 1) * wb_sample_bytes(p);
+  std::vector<uint16_t> rows(row * w->C);
+  std::vector<uint32_t> fpos(w->C);
+  for (int c = 0; c < w->C; ++c) {
+    if (w->rational) wbr_weight_rows(w->rp, freq_hz[c], rows.data() + row * c);
+    else wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
+    fpos[c] = wb_freq_mod(p, freq_hz[c]);
+  }
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->d_w), rows.size() * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_fpos), fpos.size() * sizeof(uint32_t));
+  for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&w->d_hist[b], hist_bytes);
+  const size_t sm_bytes = static_cast<size_t>(w->C) * 2 * sizeof(float);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_sm), sm_bytes);
+  if (e != hipSuccess) {
+    h->err = std::string(who) + ": hipMalloc failed: " + hipGetErrorString(e);
+    wb_free(w);
+    return FMX_E_NOMEM;
+  }
+  e = hipHostMalloc(reinterpret_cast<void **>(&w->stage), row * sizeof(uint16_t) + sizeof(uint32_t), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev, hipEventDisableTiming);
+  // synchronous copies: the tables are complete before the first call is queued
+  if (e == hipSuccess) e = hipMemcpy(w->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(w->d_fpos, fpos.data(), fpos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  // the smoothers' only readers run on sA: cleared there, ahead of the first of them
+  if (e == hipSuccess) e = hipMemsetAsync(w->d_sm, 0, sm_bytes, h->sA);
+  if (e != hipSuccess) {
+    h->err = std::string(who) + ": " + hipGetErrorString(e);
+    wb_free(w);
+    return FMX_E_HIP;
+  }
+  *wb = w;
+  return FMX_OK;
+}
 } // namespace
 
 int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, int n_channels, void **wb) {
@@ -1978,48 +2039,40 @@ int fmx_wb_create(void *handle, const fmx_wb_config *cfg, const int *freq_hz, in
   WbPlan p;
   int rc = wb_plan(*cfg, &p, &h->err);
   if (rc != FMX_OK) return rc;
-  for (int c = 0; c < n_channels; ++c)
-    if (!wb_freq_ok(p, freq_hz[c])) {
-      h->err = "fmx_wb_create: channel " + std::to_string(c) + " lies outside +- wide_rate / 2";
-      return FMX_E_INVALID;
-    }
-  HIP_TRY(hipSetDevice(h->device));
   Wb *w = new (std::nothrow) Wb();
   if (!w) return FMX_E_NOMEM;
   w->h = h;
   w->p = p;
   w->C = n_channels;
-  const size_t row = static_cast<size_t>(4) * p.Lp, hist_bytes = static_cast<size_t>(p.L - 1) * wb_sample_bytes(p);
-  std::vector<uint16_t> rows(row * n_channels);
-  std::vector<uint32_t> fpos(n_channels);
-  for (int c = 0; c < n_channels; ++c) {
-    wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
-    fpos[c] = wb_freq_mod(p, freq_hz[c]);
+  return wb_create_finish(w, freq_hz, "fmx_wb_create", wb);
+}
+
+int fmx_wb_create_rational(void *handle, const fmx_wb_config *cfg, const int *freq_hz, int n_channels, void **wb) {
+  Handle *h = H(handle);
+  if (wb) *wb = nullptr;
+  if (!h) return FMX_E_INVALID;
+  if (!cfg || !freq_hz || !wb || n_channels < 1) {
+    h->err = "fmx_wb_create_rational: null argument or no channels";
+    return FMX_E_INVALID;
   }
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->d_w), rows.size() * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_fpos), fpos.size() * sizeof(uint32_t));
-  for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&w->d_hist[b], hist_bytes);
-  const size_t sm_bytes = static_cast<size_t>(n_channels) * 2 * sizeof(float);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_sm), sm_bytes);
-  if (e != hipSuccess) {
-    h->err = std::string("fmx_wb_create: hipMalloc failed: ") + hipGetErrorString(e);
-    wb_free(w);
-    return FMX_E_NOMEM;
-  }
-  e = hipHostMalloc(reinterpret_cast<void **>(&w->stage), row * sizeof(uint16_t) + sizeof(uint32_t), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev, hipEventDisableTiming);
-  // synchronous copies: the tables are complete before the first call is queued
-  if (e == hipSuccess) e = hipMemcpy(w->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(w->d_fpos, fpos.data(), fpos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  // the smoothers' only readers run on sA: cleared there, ahead of the first of them
-  if (e == hipSuccess) e = hipMemsetAsync(w->d_sm, 0, sm_bytes, h->sA);
-  if (e != hipSuccess) {
-    h->err = std::string("fmx_wb_create: ") + hipGetErrorString(e);
-    wb_free(w);
-    return FMX_E_HIP;
-  }
-  *wb = w;
-  return FMX_OK;
+  WbrPlan q;
+  int rc = wbr_plan(*cfg, &q, &h->err);
+  if (rc != FMX_OK) return rc;
+  if (q.Q == 1) return fmx_wb_create(handle, cfg, freq_hz, n_channels, wb); // an integer ratio: k_wb's object
+  Wb *w = new (std::nothrow) Wb();
+  if (!w) return FMX_E_NOMEM;
+  w->h = h;
+  w->rational = true;
+  w->rp = q;
+  // what the shared calls read of the integer plan; D and L stay 0 (no integer ratio)
+  w->p.fs = q.fs;
+  w->p.format = q.format;
+  w->p.block = q.block;
+  w->p.sexp = q.sexp;
+  w->p.Lp = q.Lp;
+  w->p.tpp = q.tpp;
+  w->C = n_channels;
+  return wb_create_finish(w, freq_hz, "fmx_wb_create_rational", wb);
 }
 
 int fmx_wb_destroy(void *wb) {
@@ -2039,8 +2092,9 @@ int fmx_wb_set_freq(void *wb, int channel, int freq_hz) {
     return FMX_E_INVALID;
   }
   if (w->ev_set) HIP_TRY(hipEventSynchronize(w->ev)); // the staging image's last copy has left it
-  const size_t row = static_cast<size_t>(4) * w->p.Lp;
-  wb_weight_rows(w->p, freq_hz, w->stage);
+  const size_t row = static_cast<size_t>(4) * w->p.Lp * (w->rational ? w->rp.Q : 1);
+  if (w->rational) wbr_weight_rows(w->rp, freq_hz, w->stage);
+  else wb_weight_rows(w->p, freq_hz, w->stage);
   const uint32_t fm = wb_freq_mod(w->p, freq_hz);
   std::memcpy(w->stage + row, &fm, sizeof(fm));
   // on the stage stream: after the calls queued so far, before later ones
@@ -2076,6 +2130,10 @@ int fmx_wb_process(void *wb, const void *d_wide, int n_out, float *d_out, int ou
     h->err = "fmx_wb_process: n_out exceeds the object's block";
     return FMX_E_CAPACITY;
   }
+  if (w->rational && n_out % w->rp.Q != 0) {
+    h->err = "fmx_wb_process: n_out must be a multiple of Q = " + std::to_string(w->rp.Q) + " (wide_rate / dsp_rate = P / Q)";
+    return FMX_E_INVALID;
+  }
   if (n_out == 0) return FMX_OK;
   int rc;
   if ((rc = join_into_A(h)) != FMX_OK) return rc;
@@ -2089,13 +2147,19 @@ int fmx_wb_process_block(void *wb, const void *d_wide, int n, const fmx_block_ou
   const WbPlan &p = w->p;
   const char *bad = nullptr;
   if (h->M != 1) bad = "the handle's iq_rate must equal its dsp_rate";
-  else if (p.fs / p.D != h->cfg.dsp_rate) bad = "the channelizer's dsp_rate is not the handle's";
+  else if (w->rational ? static_cast<int64_t>(p.fs) * w->rp.Q != static_cast<int64_t>(h->cfg.dsp_rate) * w->rp.P
+                       : p.fs / p.D != h->cfg.dsp_rate)
+    bad = "the channelizer's dsp_rate is not the handle's";
   else if (w->C != h->C) bad = "the channelizer's channel count is not the handle's";
   else if (n < 0 || (n > 0 && !d_wide)) bad = "null input or negative n";
   else if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count) bad = "d_pcm_l, d_pcm_r and d_pcm_count are required";
   else if (o->d_signal) bad = "d_signal must be NULL (fmx_wb_signal, called behind this call, delivers every station's RF level)";
   if (bad) {
     h->err = std::string("fmx_wb_process_block: ") + bad;
+    return FMX_E_INVALID;
+  }
+  if (w->rational && n % w->rp.Q != 0) {
+    h->err = "fmx_wb_process_block: n must be a multiple of Q = " + std::to_string(w->rp.Q) + " (wide_rate / dsp_rate = P / Q)";
     return FMX_E_INVALID;
   }
   if (n > std::min(h->cfg.block, p.block)) {
@@ -2146,33 +2210,63 @@ namespace {
 int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, const char *who) {
   Handle *h = w->h;
   const WbPlan &p = w->p;
+  const int s16 = p.format == FMX_WB_S16;
+  const uint32_t base_mod = static_cast<uint32_t>(w->counter % static_cast<uint64_t>(p.fs));
+  const float scale = static_cast<float>(std::ldexp(s16 ? 1.0 / 32768.0 : 1.0 / 255.0, -p.sexp));
   int rc;
-  WbArgs a{};
-  a.in = d_wide;
-  a.s16 = p.format == FMX_WB_S16;
-  a.D = p.D;
-  a.L = p.L;
-  a.Lp = p.Lp;
-  a.n_out = n_out;
-  a.C = w->C;
-  a.w = w->d_w;
-  a.fpos = w->d_fpos;
-  a.hist = w->d_hist[w->cur];
-  a.hist_out = w->d_hist[w->cur ^ 1];
-  a.valid = w->valid;
-  a.fs = static_cast<uint32_t>(p.fs);
-  a.base_mod = static_cast<uint32_t>(w->counter % static_cast<uint64_t>(p.fs));
-  a.inv_fs = 1.0 / static_cast<double>(p.fs);
-  a.scale = static_cast<float>(std::ldexp(a.s16 ? 1.0 / 32768.0 : 1.0 / 255.0, -p.sexp));
-  a.out = d_out;
-  a.out_stride = out_stride;
-  if ((rc = launch_wb(a, h->sA)) != FMX_OK) {
+  if (w->rational) { // k_wbr: the Q phases' rows, a_r and the longest phase's history
+    const WbrPlan &q = w->rp;
+    WbrArgs a{};
+    a.in = d_wide;
+    a.s16 = s16;
+    a.P = q.P;
+    a.Q = q.Q;
+    a.Lh = q.Lh;
+    a.Lp = q.Lp;
+    a.n_out = n_out;
+    a.C = w->C;
+    for (int r = 0; r < q.Q; ++r) a.a[r] = q.a[r];
+    a.w = w->d_w;
+    a.fpos = w->d_fpos;
+    a.hist = w->d_hist[w->cur];
+    a.hist_out = w->d_hist[w->cur ^ 1];
+    a.valid = w->valid;
+    a.fs = static_cast<uint32_t>(p.fs);
+    a.base_mod = base_mod;
+    a.inv_fs = 1.0 / static_cast<double>(p.fs);
+    a.scale = scale;
+    a.out = d_out;
+    a.out_stride = out_stride;
+    rc = launch_wbr(a, h->sA);
+  } else {
+    WbArgs a{};
+    a.in = d_wide;
+    a.s16 = s16;
+    a.D = p.D;
+    a.L = p.L;
+    a.Lp = p.Lp;
+    a.n_out = n_out;
+    a.C = w->C;
+    a.w = w->d_w;
+    a.fpos = w->d_fpos;
+    a.hist = w->d_hist[w->cur];
+    a.hist_out = w->d_hist[w->cur ^ 1];
+    a.valid = w->valid;
+    a.fs = static_cast<uint32_t>(p.fs);
+    a.base_mod = base_mod;
+    a.inv_fs = 1.0 / static_cast<double>(p.fs);
+    a.scale = scale;
+    a.out = d_out;
+    a.out_stride = out_stride;
+    rc = launch_wb(a, h->sA);
+  }
+  if (rc != FMX_OK) {
     h->err = std::string(who) + ": kernel launch failed";
     return rc;
   }
-  const int64_t n_in = static_cast<int64_t>(n_out) * p.D;
+  const int64_t n_in = wb_consumed(w, n_out), kept = w->rational ? w->rp.Lh - 1 : p.L - 1;
   w->cur ^= 1;
-  w->valid = static_cast<int>(std::min<int64_t>(p.L - 1, w->valid + n_in));
+  w->valid = static_cast<int>(std::min<int64_t>(kept, w->valid + n_in));
   w->counter += static_cast<uint64_t>(n_in);
   // the call fmx_wb_signal measures
   w->sig_wide = d_wide;
@@ -2200,7 +2294,8 @@ int fmx_wb_signal(void *wb, fmx_signal_level *d_level) {
   }
   HIP_TRY(hipSetDevice(h->device));
   if (!w->d_clip) {
-    const size_t n_clip = static_cast<size_t>(wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D)) * 2;
+    const long most = w->rational ? static_cast<long>(wb_consumed(w, p.block)) : static_cast<long>(p.block) * p.D;
+    const size_t n_clip = static_cast<size_t>(wb_scan_clip_workgroups(most)) * 2;
     if (hipMalloc(reinterpret_cast<void **>(&w->d_clip), n_clip * sizeof(uint32_t)) != hipSuccess) {
       w->d_clip = nullptr;
       h->err = "fmx_wb_signal: hipMalloc failed";
@@ -2216,6 +2311,7 @@ int fmx_wb_signal(void *wb, fmx_signal_level *d_level) {
   a.in = w->sig_wide;
   a.s16 = p.format == FMX_WB_S16;
   a.D = p.D;
+  if (w->rational) a.n_in = static_cast<long>(wb_consumed(w, w->sig_n)); // the call's n P / Q raw samples
   a.clip = w->d_clip;
   a.sm = w->d_sm;
   a.level = d_level;

@@ -328,6 +328,68 @@ struct WbArgs {
 };
 int launch_wb(const WbArgs &a, void *stream);
 
+// ---- rational-rate channelizer (fmx_wb_design.cpp, fmx_wb_rational.inc) ----
+// wide_rate / dsp_rate = P / Q in lowest terms: Q integer channelizers of
+// decimation P whose outputs interleave.  Output n = Q m + r ends at wide
+// sample i0 = m P + a_r and uses the taps h[Q j + b_r], r P = Q a_r + b_r.
+#define FMX_WBR_QMAX 16
+constexpr int kWbLdsMax = 80 * 1024; // WB_LDS_MAX (fmx_wb.inc)
+constexpr int kWbNtMax = 16;         // WB_NT_MAX
+struct WbrPlan {
+  int P = 0, Q = 0, tpp = 0, Lup = 0, Lp = 0; // Lp: the largest L_r rounded up to the MFMA's K = 32
+  int Lh = 0;                        // the largest L_r: the history holds Lh - 1 raw samples
+  int fs = 0, format = 0, block = 0;
+  int sexp = 0;                      // one scale for every phase's tables
+  float fc = 0.0f;
+  int a[FMX_WBR_QMAX] = {}, b[FMX_WBR_QMAX] = {}, Lr[FMX_WBR_QMAX] = {};
+  std::vector<double> g;             // Q 2 fc h[k], k = 0..Lup-1, at the up-sampled rate Q Fs
+};
+// taps = false: the geometry alone (g and sexp stay empty)
+int wbr_plan(const fmx_wb_config &cfg, WbrPlan *p, std::string *err, bool taps = true);
+// one channel's rows [Q][4][Lp]: phase r's entry kk holds tap j = Lp - 1 - kk
+// (zero for j >= L_r), W_r[j] = g[Q j + b_r] e^{+j 2 pi f j / Fs}
+void wbr_weight_rows(const WbrPlan &p, int freq_hz, uint16_t *rows);
+// W_r[j] (re, im), j = 0..L_r-1, read back from such rows
+void wbr_rows_to_taps(const WbrPlan &p, const uint16_t *rows, int phase, float *out);
+// The kernel's tiling.  Tile T = mb Q + r is the 16 outputs (16 mb + col) Q + r;
+// workgroup w takes the tiles [w nt, (w + 1) nt) and stages the wide samples
+// from 16 mb0 P - (Lp - 1) on, mb0 its first tile's mb.
+// k_wbr, its launcher and fmx_wb_rational_geometry all compute with these.
+constexpr int wbr_window(int P, int a_last, int Lp, int mb0, int mb1) { return (16 * (mb1 - mb0) + 15) * P + a_last + Lp; }
+struct WbrGroup {
+  int T0, T1; // the workgroup's first and last tile
+  int mb0;    // the block of 16 outputs per phase its image starts at
+  int window; // samples it stages
+};
+constexpr WbrGroup wbr_group(int wg, int nt, int ntiles, int P, int Q, int a_last, int Lp) {
+  const int T0 = wg * nt, T1 = (T0 + nt < ntiles ? T0 + nt : ntiles) - 1;
+  return WbrGroup{T0, T1, T0 / Q, wbr_window(P, a_last, Lp, T0 / Q, T1 / Q)};
+}
+// where tile T's column 0 starts in the image of a workgroup whose image starts at block mb0
+constexpr int wbr_tile_offset(int P, int Q, int a_r, int T, int mb0) { return 16 * (T / Q - mb0) * P + a_r; }
+// tiles per workgroup: as many as fit WB_LDS_MAX wherever the workgroup starts, at most WB_NT_MAX and what the call needs
+int wbr_tiles(int P, int Q, int a_last, int Lp, int s16, int n_out);
+
+struct WbrArgs {
+  const void *in;       // n_out P / Q wide samples, interleaved I/Q
+  int s16, in_al;       // as WbArgs
+  int P, Q, Lh, Lp, n_out, C; // n_out a multiple of Q
+  int a[FMX_WBR_QMAX];  // a_r
+  const uint16_t *w;    // [C][Q][4][Lp] weight rows
+  const uint32_t *fpos; // [C] f mod Fs
+  const void *hist;     // the last Lh - 1 raw samples before this call
+  void *hist_out;
+  int valid;
+  uint32_t fs, base_mod;
+  double inv_fs;
+  float scale;
+  float *out;
+  int out_stride;
+  int nt, ntiles;       // tiles per workgroup, tiles of the call (set by the launcher)
+  long n_in;            // n_out P / Q (set by the launcher)
+};
+int launch_wbr(const WbrArgs &a, void *stream);
+
 // ---- band scan (fmx_wb_scan.inc; plan and weight rows are the channelizer's) ----
 struct WbScanArgs {
   const void *in;          // n_out * D wide samples, interleaved I/Q
@@ -358,6 +420,7 @@ struct WbLevelArgs {
   fmx_signal_level *level; // [C]
   double sp[4];            // gain*factor, bias, floor, ceil
   int nclip;               // clip workgroups (set by the launcher)
+  long n_in;               // the call's raw samples when they are not n * D (a rational object: n P / Q; D is then unused); 0: n * D
 };
 int launch_wb_level(const WbLevelArgs &a, void *stream);
 

@@ -116,6 +116,114 @@ void wb_rows_to_taps(const WbPlan &p, const uint16_t *rows, float *out) {
   }
 }
 
+// ---- rational rates ----
+// wide_rate / dsp_rate = P / Q in lowest terms.  The prototype is designed at
+// the up-sampled rate Q Fs: Lup = P tpp taps, fc = min(0.45 / P, 0.45), gain
+// Q 2 fc.  Output n = Q m + r uses the taps h[Q j + b_r] on x[m P + a_r - j],
+// r P = Q a_r + b_r: Q integer channelizers of decimation P.  With Q = 1 every
+// number below is wb_plan's.
+int wbr_plan(const fmx_wb_config &cfg, WbrPlan *p, std::string *err, bool taps) {
+  auto fail = [&](const char *m) {
+    if (err) *err = m;
+    return FMX_E_INVALID;
+  };
+  if (cfg.dsp_rate <= 0 || cfg.wide_rate <= 0) return fail("fmx_wb: rates must be positive");
+  int g = cfg.wide_rate, t = cfg.dsp_rate;
+  while (t != 0) {
+    const int u = g % t;
+    g = t;
+    t = u;
+  }
+  const int P = cfg.wide_rate / g, Q = cfg.dsp_rate / g;
+  if (Q > FMX_WBR_QMAX) return fail("fmx_wb: wide_rate / dsp_rate = P / Q in lowest terms needs Q <= 16");
+  if (P < 2 * Q || P > 128 * Q) return fail("fmx_wb: wide_rate / dsp_rate must be 2..128");
+  const int tpp = cfg.taps_per_phase == 0 ? (P >= 8 * Q ? 28 : (P >= 4 * Q ? 20 : 12)) : cfg.taps_per_phase;
+  if (tpp < 4 || tpp > 28) return fail("fmx_wb: taps_per_phase must be 0 or 4..28");
+  if (cfg.format != FMX_WB_U8 && cfg.format != FMX_WB_S16) return fail("fmx_wb: unknown sample format");
+  if (cfg.block < 1) return fail("fmx_wb: block must be at least 1");
+  p->P = P;
+  p->Q = Q;
+  p->tpp = tpp;
+  p->Lup = P * tpp;
+  p->fs = cfg.wide_rate;
+  p->format = cfg.format;
+  p->block = cfg.block;
+  p->Lh = 0;
+  for (int r = 0; r < Q; ++r) {
+    p->a[r] = r * P / Q;
+    p->b[r] = r * P % Q;
+    p->Lr[r] = (p->Lup - p->b[r] + Q - 1) / Q;
+    p->Lh = std::max(p->Lh, p->Lr[r]);
+  }
+  p->Lp = (p->Lh + 31) & ~31;
+  // one tile's window: 16 outputs P samples apart, the last phase's offset, Lp taps
+  const int window = (wbr_window(P, p->a[Q - 1], p->Lp, 0, 0) + 7) & ~7;
+  if (static_cast<long>(window) * (cfg.format == FMX_WB_S16 ? 8 : 4) > kWbLdsMax)
+    return fail(cfg.format == FMX_WB_S16
+                    ? "fmx_wb: one tile's window (15 P + a_{Q-1} + Lp int16 samples of 8 bytes) exceeds 80 KB of LDS"
+                    : "fmx_wb: one tile's window (15 P + a_{Q-1} + Lp u8 samples of 4 bytes) exceeds 80 KB of LDS");
+  p->fc = std::min(0.45f / static_cast<float>(P), 0.45f);
+  if (!taps) return FMX_OK;
+  std::vector<float> h(p->Lup);
+  firdes_kaiser(static_cast<unsigned>(p->Lup), p->fc, 80.0f, 0.0f, h.data());
+  const double scale = static_cast<double>(Q) * static_cast<double>(2.0f * p->fc);
+  p->g.resize(p->Lup);
+  // every k = Q j + b_r belongs to exactly one phase (b_r runs through all
+  // residues): the largest |W| over every phase is the largest |g|
+  double gmax = 0.0;
+  for (int k = 0; k < p->Lup; ++k) {
+    p->g[k] = scale * static_cast<double>(h[k]);
+    gmax = std::max(gmax, std::fabs(p->g[k]));
+  }
+  if (!(gmax > 0.0)) return fail("fmx_wb: degenerate filter");
+  p->sexp = 13 - std::ilogb(gmax);
+  return FMX_OK;
+}
+
+void wbr_weight_rows(const WbrPlan &p, int freq_hz, uint16_t *rows) {
+  std::memset(rows, 0, sizeof(uint16_t) * 4 * p.Lp * p.Q);
+  int64_t fm = static_cast<int64_t>(freq_hz) % p.fs;
+  if (fm < 0) fm += p.fs;
+  for (int r = 0; r < p.Q; ++r) {
+    uint16_t *rr = rows + static_cast<size_t>(4) * p.Lp * r;
+    for (int j = 0; j < p.Lr[r]; ++j) {
+      const double gk = p.g[p.Q * j + p.b[r]];
+      const int64_t turns = (fm * j) % p.fs; // (f j mod Fs) / Fs turns, exact
+      const double ph = kTwoPi * static_cast<double>(turns) / static_cast<double>(p.fs);
+      const double w[2] = {std::ldexp(gk * std::cos(ph), p.sexp), std::ldexp(gk * std::sin(ph), p.sexp)};
+      const int kk = p.Lp - 1 - j;
+      for (int c = 0; c < 2; ++c) {
+        const uint16_t hi = wb_f16_bits(w[c]);
+        rr[(2 * c) * p.Lp + kk] = hi;
+        rr[(2 * c + 1) * p.Lp + kk] = wb_f16_bits(w[c] - wb_f16_value(hi));
+      }
+    }
+  }
+}
+
+void wbr_rows_to_taps(const WbrPlan &p, const uint16_t *rows, int phase, float *out) {
+  const uint16_t *rr = rows + static_cast<size_t>(4) * p.Lp * phase;
+  for (int j = 0; j < p.Lr[phase]; ++j) {
+    const int kk = p.Lp - 1 - j;
+    for (int c = 0; c < 2; ++c)
+      out[2 * j + c] = static_cast<float>(
+          std::ldexp(wb_f16_value(rr[(2 * c) * p.Lp + kk]) + wb_f16_value(rr[(2 * c + 1) * p.Lp + kk]), -p.sexp));
+  }
+}
+
+int wbr_tiles(int P, int Q, int a_last, int Lp, int s16, int n_out) {
+  const long cap = kWbLdsMax / (s16 ? 8 : 4); // samples of the window
+  const long M = (n_out / Q + 15) / 16;       // blocks of 16 outputs per phase
+  int nt = 0;
+  // nt consecutive tiles span at most 1 + ceil((nt - 1) / Q) blocks (a workgroup starting at the last phase)
+  for (int k = 1; k <= kWbNtMax && k <= M * Q; ++k) {
+    const int span = 1 + (k - 1 + Q - 1) / Q;
+    if (((static_cast<long>(wbr_window(P, a_last, Lp, 0, span - 1)) + 7) & ~7L) > cap) break;
+    nt = k;
+  }
+  return nt;
+}
+
 int wb_scan_plan(const fmx_wb_scan_config &cfg, WbPlan *p, std::string *err) {
   auto fail = [&](const char *m) {
     if (err) *err = m;
@@ -184,6 +292,66 @@ extern "C" int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int mi
     ++count;
   }
   return count;
+}
+
+extern "C" int fmx_wb_ratio(const fmx_wb_config *cfg, int *P, int *Q, int *taps) {
+  if (!cfg) return FMX_E_INVALID;
+  fmx::WbrPlan p;
+  const int rc = fmx::wbr_plan(*cfg, &p, nullptr, false);
+  if (rc != FMX_OK) return rc;
+  if (P) *P = p.P;
+  if (Q) *Q = p.Q;
+  if (taps) *taps = p.Lh;
+  return FMX_OK;
+}
+
+extern "C" int fmx_wb_weights_rational(const fmx_wb_config *cfg, int freq_hz, int phase, float *out, int cap) {
+  if (!cfg) return FMX_E_INVALID;
+  fmx::WbrPlan p;
+  const int rc = fmx::wbr_plan(*cfg, &p, nullptr);
+  if (rc != FMX_OK) return rc;
+  if (phase < 0 || phase >= p.Q) return FMX_E_INVALID;
+  if (2 * static_cast<int64_t>(freq_hz) > p.fs || 2 * static_cast<int64_t>(freq_hz) < -static_cast<int64_t>(p.fs))
+    return FMX_E_INVALID;
+  const int n = 2 * p.Lr[phase];
+  if (!out || cap < n) return n;
+  std::vector<uint16_t> rows(static_cast<size_t>(4) * p.Lp * p.Q);
+  fmx::wbr_weight_rows(p, freq_hz, rows.data());
+  fmx::wbr_rows_to_taps(p, rows.data(), phase, out);
+  return n;
+}
+
+extern "C" int fmx_wb_rational_geometry(const fmx_wb_config *cfg, int n_out, int *out, int cap) {
+  if (!cfg) return FMX_E_INVALID;
+  fmx::WbrPlan p;
+  const int rc = fmx::wbr_plan(*cfg, &p, nullptr, false);
+  if (rc != FMX_OK) return rc;
+  if (n_out < 1 || n_out % p.Q != 0 || n_out > p.block) return FMX_E_INVALID;
+  const int s16 = p.format == FMX_WB_S16;
+  const int nt = fmx::wbr_tiles(p.P, p.Q, p.a[p.Q - 1], p.Lp, s16, n_out);
+  if (nt < 1) return FMX_E_INVALID;
+  const int ntiles = (n_out / p.Q + 15) / 16 * p.Q;
+  const int need = 6 + 4 * ntiles;
+  if (!out || cap < need) return need;
+  int wmax = 0;
+  for (int T = 0; T < ntiles; ++T) {
+    // the workgroup's frame and the tile's place in it, from the functions k_wbr itself calls
+    const fmx::WbrGroup wg = fmx::wbr_group(T / nt, nt, ntiles, p.P, p.Q, p.a[p.Q - 1], p.Lp);
+    const int r = T % p.Q;
+    wmax = std::max(wmax, wg.window);
+    int *o = out + 6 + 4 * T;
+    o[0] = r;
+    o[1] = p.a[r];
+    o[2] = fmx::wbr_tile_offset(p.P, p.Q, p.a[r], T, wg.mb0);
+    o[3] = wg.window;
+  }
+  out[0] = nt;
+  out[1] = wmax;
+  out[2] = ((wmax + 7) & ~7) * (s16 ? 8 : 4);
+  out[3] = (ntiles + nt - 1) / nt;
+  out[4] = ntiles;
+  out[5] = p.Lp;
+  return need;
 }
 
 extern "C" int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap) {

@@ -65,7 +65,7 @@ template <int W> __global__ __launch_bounds__(256) void k_wb_level(WbLevelArgs a
     hard += a.clip[2 * k];
     nearc += a.clip[2 * k + 1];
   }
-  const double nn = (double)((long)a.n * a.D);
+  const double nn = (double)a.n_in; // the call's raw samples
   const double pw = sum / (double)a.n;
   const double *sp = a.sp; // gain*factor, bias, floor, ceil
   // the record as k_wb_scan_level forms it (signal_level.cpp:187-195, no mean removed)
@@ -96,15 +96,21 @@ template <int W> __global__ __launch_bounds__(256) void k_wb_level(WbLevelArgs a
 // it is: it reads in, n_out, D and clip alone), then one workgroup per channel
 int launch_wb_level(const WbLevelArgs &a0, void *stream) {
   WbLevelArgs a = a0;
-  if (a.C <= 0 || a.n <= 0 || a.stride < a.n || a.D < 1 || !a.rows || !a.in || !a.clip || !a.sm || !a.level)
+  if (a.C <= 0 || a.n <= 0 || a.stride < a.n || (a.n_in == 0 && a.D < 1) || !a.rows || !a.in || !a.clip || !a.sm || !a.level)
     return FMX_E_INVALID;
   if ((reinterpret_cast<uintptr_t>(a.rows) & 3) || (reinterpret_cast<uintptr_t>(a.level) & 7)) return FMX_E_INVALID;
-  a.nclip = wb_scan_clip_workgroups((long)a.n * a.D);
-  hipStream_t st = static_cast<hipStream_t>(stream);
   WbScanArgs s{};
   s.in = a.in;
   s.n_out = a.n;
   s.D = a.D;
+  if (a.n_in == 0) a.n_in = (long)a.n * a.D;
+  else { // a rational object's call: its n_in raw samples, counted as n_in x 1
+    if (a.n_in < 0 || a.n_in > 0x7FFFFFFFL) return FMX_E_INVALID;
+    s.n_out = (int)a.n_in;
+    s.D = 1;
+  }
+  a.nclip = wb_scan_clip_workgroups(a.n_in);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   s.clip = a.clip;
   if (a.s16) hipLaunchKernelGGL(k_wb_scan_clip<int16_t>, dim3((unsigned)a.nclip), dim3(256), 0, st, s);
   else hipLaunchKernelGGL(k_wb_scan_clip<uint8_t>, dim3((unsigned)a.nclip), dim3(256), 0, st, s);

@@ -110,6 +110,10 @@ def lib():
         "fmx_afpost": (i, [vp, vp, vp, i, i, vp, vp, i, i, vp]),
         "fmx_rds": (i, [vp, vp, i, i, vp, i, vp]),
         "fmx_wb_create": (i, [vp, C.POINTER(WbConfig), C.POINTER(i), i, C.POINTER(vp)]),
+        "fmx_wb_create_rational": (i, [vp, C.POINTER(WbConfig), C.POINTER(i), i, C.POINTER(vp)]),
+        "fmx_wb_ratio": (i, [C.POINTER(WbConfig), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "fmx_wb_weights_rational": (i, [C.POINTER(WbConfig), i, i, fp, i]),
+        "fmx_wb_rational_geometry": (i, [C.POINTER(WbConfig), i, C.POINTER(i), i]),
         "fmx_wb_destroy": (i, [vp]),
         "fmx_wb_set_freq": (i, [vp, i, i]),
         "fmx_wb_reset": (i, [vp, C.c_int64]),
@@ -329,19 +333,22 @@ def make_wb_config(wide_rate=2_400_000, dsp_rate=240_000, format=FMX_WB_S16, tap
 class Wideband:
     """The wideband channelizer of one Handle (fmx_wb_*): one wide IQ capture
     in, the complex baseband rows of len(freq_hz) tuned channels out --
-    Handle.demod's input.  Close it before its handle."""
+    Handle.demod's input.  Close it before its handle.  rational: create it
+    with fmx_wb_create_rational (wide_rate / dsp_rate = P / Q; every call's
+    output count is then a multiple of Q and consumes n P / Q samples)."""
 
-    def __init__(self, handle, wcfg, freq_hz):
+    def __init__(self, handle, wcfg, freq_hz, rational=False):
         self.L = lib()
         self.handle = handle
         self.cfg = wcfg
         self.n = len(freq_hz)
         f = (C.c_int * self.n)(*[int(v) for v in freq_hz])
         w = C.c_void_p()
-        rc = self.L.fmx_wb_create(handle.h, C.byref(wcfg), f, self.n, C.byref(w))
+        name = "fmx_wb_create_rational" if rational else "fmx_wb_create"
+        rc = getattr(self.L, name)(handle.h, C.byref(wcfg), f, self.n, C.byref(w))
         self.w = w if rc == FMX_OK else None
         if rc != FMX_OK:
-            raise FmxError(f"fmx_wb_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+            raise FmxError(f"{name} failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
 
     def _ck(self, rc, what):
         if rc != FMX_OK:
@@ -487,6 +494,42 @@ def wb_weights(wcfg, freq_hz):
     buf = np.zeros(n, dtype=np.float32)
     lib().fmx_wb_weights(C.byref(wcfg), int(freq_hz), buf.ctypes.data_as(C.POINTER(C.c_float)), n)
     return buf.view(np.complex64)
+
+
+def wb_ratio(wcfg):
+    """fmx_wb_ratio: (P, Q, taps of the longest phase) of wide_rate / dsp_rate = P / Q."""
+    P, Q, taps = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().fmx_wb_ratio(C.byref(wcfg), C.byref(P), C.byref(Q), C.byref(taps))
+    if rc != FMX_OK:
+        raise FmxError(f"fmx_wb_ratio failed ({rc})")
+    return P.value, Q.value, taps.value
+
+
+def wb_weights_rational(wcfg, freq_hz, phase):
+    """fmx_wb_weights_rational: phase's W_r[j] as complex64 [L_r], read back from the f16 tables."""
+    import numpy as np
+    n = lib().fmx_wb_weights_rational(C.byref(wcfg), int(freq_hz), int(phase), None, 0)
+    if n < 0:
+        raise FmxError(f"fmx_wb_weights_rational failed ({n})")
+    buf = np.zeros(n, np.float32)
+    lib().fmx_wb_weights_rational(C.byref(wcfg), int(freq_hz), int(phase), buf.ctypes.data_as(C.POINTER(C.c_float)), n)
+    return buf.view(np.complex64)
+
+
+def wb_rational_geometry(wcfg, n_out):
+    """fmx_wb_rational_geometry: the tiling of a call of n_out outputs as a
+    dict (nt, window, lds_bytes, workgroups, tiles, Lp) with "tile": int32
+    [tiles][4] of (phase, a_r, image offset, its workgroup's window)."""
+    import numpy as np
+    n = lib().fmx_wb_rational_geometry(C.byref(wcfg), int(n_out), None, 0)
+    if n < 0:
+        raise FmxError(f"fmx_wb_rational_geometry failed ({n})")
+    buf = np.zeros(n, np.int32)
+    lib().fmx_wb_rational_geometry(C.byref(wcfg), int(n_out), buf.ctypes.data_as(C.POINTER(C.c_int)), n)
+    keys = ("nt", "window", "lds_bytes", "workgroups", "tiles", "Lp")
+    g = {k: int(v) for k, v in zip(keys, buf[:6])}
+    g["tile"] = buf[6:].reshape(-1, 4)
+    return g
 
 
 def make_wb_scan_config(wide_rate=2_400_000, dsp_rate=240_000, format=FMX_WB_S16, taps_per_phase=0, block=4096,

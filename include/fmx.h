@@ -47,7 +47,9 @@
 extern "C" {
 #endif
 
-/* ABI history: the capture bank (fmx_wb_bank_*: many wide captures channelized in one call) arrived at 13
+/* ABI history: rational wide rates (fmx_wb_create_rational, fmx_wb_ratio, fmx_wb_weights_rational,
+ * fmx_wb_rational_geometry: 20, 10 and 2.048 MS/s captures channelized at P / Q) arrived at 13 without a bump,
+ * as the bank did: additions only; the capture bank (fmx_wb_bank_*: many wide captures channelized in one call) arrived at 13
  * without a bump: its symbols are additions, no existing symbol, struct or enum changed, and a caller built
  * against the earlier 13 runs unchanged (a caller that needs the bank looks its symbols up);
  * 13 adds the band receiver's RF level (fmx_wb_signal, fmx_wb_set_signal_params,
@@ -242,7 +244,7 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
  * written. */
 enum { FMX_WB_U8 = 0, FMX_WB_S16 = 1 };
 typedef struct {
-  int wide_rate;      /* integer multiple D of dsp_rate, 2 <= D <= 128             */
+  int wide_rate;      /* integer multiple D of dsp_rate, 2 <= D <= 128 (P / Q of it: fmx_wb_create_rational) */
   int dsp_rate;
   int format;         /* FMX_WB_*                                                  */
   int taps_per_phase; /* 4..28; 0: the reference's rule (28 from D = 8, 20 from 4, else 12) */
@@ -330,6 +332,52 @@ int fmx_wb_signal_reset(void *wb, int channel);
  * k = 0..L-1, as 2L floats (re, im) read back from the kernel's f16 hi + lo
  * tables.  Returns 2L (negative on error). */
 int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap);
+
+/* ---- rational rates: wide_rate / dsp_rate = P / Q in lowest terms ----
+ * fmx_wb_create refuses a wide_rate that is no multiple of dsp_rate;
+ * fmx_wb_create_rational takes it (20 MS/s to 240 kHz is 250 / 3, 10 MS/s
+ * 125 / 3, 2.048 MS/s 128 / 15, 2 MS/s 25 / 3).  The prototype is designed at
+ * the up-sampled rate Q wide_rate: Lup = P taps_per_phase taps h =
+ * firdes_kaiser(Lup, fc, 80 dB), fc = min(0.45 / P, 0.45), gain G = Q 2 fc
+ * (taps_per_phase 0: 28 from P / Q = 8, 20 from 4, else 12), and output n is
+ * "mix, then interpolate by Q and decimate by P":
+ *   y_c[n] = G sum_i h[nP - iQ] x[i] exp(-j 2 pi f_c i / wide_rate),  0 <= nP - iQ < Lup
+ * with x and i as above.  Q = 1 is fmx_wb_create's formula term for term, and
+ * there fmx_wb_create_rational is fmx_wb_create (the same object, rows bit for
+ * bit).  Accepted: Q <= 16, 2 <= P / Q <= 128, and one tile's window of
+ * 15 P + a + Lp samples (a = floor((Q - 1) P / Q), Lp = ceil(Lup / Q) rounded
+ * up to 32) within 80 KB at 8 bytes per int16 sample, 4 per u8 sample: 10 MS/s
+ * to 256 kHz (625 / 16) is refused for FMX_WB_S16 and legal for FMX_WB_U8.
+ * Every other ratio is FMX_E_INVALID, the message naming the condition.
+ * The object is an fmx_wb object: fmx_wb_destroy, _set_freq, _reset, _process,
+ * _process_block, _signal, _set_signal_params and _signal_reset take it.  What
+ * differs at Q > 1: n_out (n of fmx_wb_process_block) must be a multiple of Q,
+ * else FMX_E_INVALID with a message naming Q -- so every call starts at phase 0
+ * and consumes the integer n_out P / Q wide samples; block need not be a
+ * multiple of Q; fmx_wb_process_block's rate condition is wide_rate Q ==
+ * dsp_rate P (the fast front end still needs n >= 1024 and n % 4 == 0, e.g.
+ * n = 4092 at Q = 3); fmx_wb_signal's clip ratios are over the call's n P / Q
+ * raw samples; the history holds ceil(Lup / Q) - 1 raw samples.
+ * Out of scope: the capture bank and the band scan stay integer (the scan's
+ * dsp_rate is free, so a 20 MS/s scan at 200 kHz needs no rational plan); and
+ * there is no int8 format -- a HackRF caller flips bit 7 of each byte and
+ * passes FMX_WB_U8.  These symbols arrived without a bump of FMX_ABI_VERSION
+ * (see above). */
+int fmx_wb_create_rational(void *handle, const fmx_wb_config *cfg, const int *freq_hz, int n_channels, void **wb);
+/* host only: P, Q and the taps of the longest phase; FMX_OK or FMX_E_INVALID */
+int fmx_wb_ratio(const fmx_wb_config *cfg, int *P, int *Q, int *taps);
+/* host only: phase r's weights W_r[j] = G h[Q j + b_r] exp(+j 2 pi f j /
+ * wide_rate), r P = Q a_r + b_r, j = 0..L_r-1, as 2 L_r floats (re, im) read
+ * back from the kernel's f16 hi + lo tables.  Returns 2 L_r (negative on error). */
+int fmx_wb_weights_rational(const fmx_wb_config *cfg, int freq_hz, int phase, float *out, int cap);
+/* host only: how a call of n_out outputs (a multiple of Q, <= block) is tiled.
+ * out[0..5]: tiles per workgroup, the largest workgroup window in samples, its
+ * LDS bytes, workgroups, tiles, Lp; then per tile T = mb Q + r (the 16 outputs
+ * (16 mb + col) Q + r) four ints: r, a_r, the offset of column 0's window in
+ * its workgroup's LDS image, that workgroup's window in samples.  Column col
+ * reads Lp samples from offset + col P on.  Returns the ints needed (nothing
+ * is written when cap is less), negative on error. */
+int fmx_wb_rational_geometry(const fmx_wb_config *cfg, int n_out, int *out, int cap);
 
 /* ---- capture bank: many wide captures of one format and rate channelized in one call ----
  * A bank holds n_captures captures of one fmx_wb_config (1..1024).  Capture s

@@ -1916,9 +1916,34 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
 
 /* ---- wideband channelizer (fmx.h; design in fmx_wb_design.cpp, kernel in fmx_wb.inc) ---- */
 namespace {
+// The first two members of Wb, WbBank and WbScan are alike, so that a call
+// handed the wrong kind of object (fmx_wb_set_iq_correction on a bank) can
+// tell and refuse.
+enum WbKind { WB_KIND_WB = 0x5742, WB_KIND_BANK = 0x5743, WB_KIND_SCAN = 0x5744 };
+// DC / IQ-imbalance correction of one object (fmx.h; kernels in fmx_wb_iqc.inc,
+// DESIGN.md section 24).  Nothing is allocated or launched while the mode has
+// never left FMX_IQC_OFF.
+struct Iqc {
+  int mode = FMX_IQC_OFF;
+  double alpha = 1.0 / 16.0;
+  FmxIqcBlock *d_blk = nullptr;   // the parameter block the corrected kernels read
+  long long *d_partial = nullptr; // [workgroups of a full block][5] the estimator's sums
+  float *d_tsum = nullptr;        // [channels or points][2] tap sums (SR, SI)
+  std::vector<float> tsum;        // the same on the host (fmx_wb_set_freq keeps both current)
+};
+void iqc_free(Iqc &q) {
+  if (q.d_blk) hipFree(q.d_blk);
+  if (q.d_partial) hipFree(q.d_partial);
+  if (q.d_tsum) hipFree(q.d_tsum);
+  q.d_blk = nullptr;
+  q.d_partial = nullptr;
+  q.d_tsum = nullptr;
+}
 struct Wb {
   Handle *h = nullptr;
+  int kind = WB_KIND_WB;
   WbPlan p;
+  Iqc iqc;
   // fmx_wb_create_rational at Q > 1: the plan is rp,
   // the rows are [C][Q][4][Lp], the history holds rp.Lh - 1 samples and a call
   // of n outputs consumes n P / Q; p carries fs, format, block, sexp and Lp
@@ -1971,6 +1996,7 @@ void wb_free(Wb *w) {
   if (w->d_rows) hipFree(w->d_rows);
   if (w->d_clip) hipFree(w->d_clip);
   if (w->d_sm) hipFree(w->d_sm);
+  iqc_free(w->iqc);
   delete w;
 }
 int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, const char *who);
@@ -2001,6 +2027,10 @@ int wb_create_finish(Wb *w, const int *freq_hz, const char *who, void **wb) {
     else wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
     fpos[c] = wb_freq_mod(p, freq_hz[c]);
   }
+  if (!w->rational) {
+    w->iqc.tsum.resize(static_cast<size_t>(2) * w->C);
+    for (int c = 0; c < w->C; ++c) wb_tap_sums(p, rows.data() + row * c, w->iqc.tsum.data() + 2 * c);
+  }
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->d_w), rows.size() * sizeof(uint16_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->d_fpos), fpos.size() * sizeof(uint32_t));
   for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&w->d_hist[b], hist_bytes);
@@ -2011,7 +2041,9 @@ int wb_create_finish(Wb *w, const int *freq_hz, const char *who, void **wb) {
     wb_free(w);
     return FMX_E_NOMEM;
   }
-  e = hipHostMalloc(reinterpret_cast<void **>(&w->stage), row * sizeof(uint16_t) + sizeof(uint32_t), hipHostMallocDefault);
+  // one channel's rows, its f mod Fs and its two tap sums
+  e = hipHostMalloc(reinterpret_cast<void **>(&w->stage), row * sizeof(uint16_t) + sizeof(uint32_t) + 2 * sizeof(float),
+                    hipHostMallocDefault);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev, hipEventDisableTiming);
   // synchronous copies: the tables are complete before the first call is queued
   if (e == hipSuccess) e = hipMemcpy(w->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
@@ -2100,6 +2132,15 @@ int fmx_wb_set_freq(void *wb, int channel, int freq_hz) {
   // on the stage stream: after the calls queued so far, before later ones
   HIP_TRY(hipMemcpyAsync(w->d_w + row * channel, w->stage, row * sizeof(uint16_t), hipMemcpyHostToDevice, h->sA));
   HIP_TRY(hipMemcpyAsync(w->d_fpos + channel, w->stage + row, sizeof(uint32_t), hipMemcpyHostToDevice, h->sA));
+  if (!w->rational) { // the channel's tap sums follow its rows (behind f mod Fs in the staging image)
+    float *ts = w->iqc.tsum.data() + 2 * static_cast<size_t>(channel);
+    wb_tap_sums(w->p, w->stage, ts);
+    if (w->iqc.d_tsum) {
+      std::memcpy(w->stage + row + 2, ts, 2 * sizeof(float));
+      HIP_TRY(hipMemcpyAsync(w->iqc.d_tsum + 2 * static_cast<size_t>(channel), w->stage + row + 2, 2 * sizeof(float),
+                             hipMemcpyHostToDevice, h->sA));
+    }
+  }
   HIP_TRY(hipEventRecord(w->ev, h->sA));
   w->ev_set = true;
   return FMX_OK;
@@ -2258,7 +2299,15 @@ int wb_run(Wb *w, const void *d_wide, int n_out, float *d_out, int out_stride, c
     a.scale = scale;
     a.out = d_out;
     a.out_stride = out_stride;
-    rc = launch_wb(a, h->sA);
+    if (w->iqc.mode == FMX_IQC_OFF) {
+      rc = launch_wb(a, h->sA);
+    } else { // estimator, finisher, corrected channelizer: the block is read on the device
+      rc = FMX_OK;
+      if (w->iqc.mode == FMX_IQC_AUTO)
+        rc = launch_iqc_estimate(d_wide, static_cast<long>(n_out) * p.D, s16, w->iqc.alpha, w->iqc.d_partial, w->iqc.d_blk,
+                                 h->sA);
+      if (rc == FMX_OK) rc = launch_wb_iqc(a, w->iqc.d_blk, w->iqc.d_tsum, h->sA);
+    }
   }
   if (rc != FMX_OK) {
     h->err = std::string(who) + ": kernel launch failed";
@@ -2356,6 +2405,7 @@ int fmx_wb_signal_reset(void *wb, int channel) {
 namespace {
 struct WbBank {
   Handle *h = nullptr;
+  int kind = WB_KIND_BANK;
   WbPlan p;
   int S = 0, C = 0, G = 0;    // captures, channels of all captures, groups
   std::vector<int> first;     // [S + 1]
@@ -2758,7 +2808,9 @@ int fmx_wb_bank_signal_reset(void *bank, int channel) {
 namespace {
 struct WbScan {
   Handle *h = nullptr;
+  int kind = WB_KIND_SCAN;
   WbPlan p;
+  Iqc iqc;
   int P = 0;                  // scan points
   uint16_t *d_w = nullptr;    // [P][4][Lp] weight rows
   float *d_partial = nullptr; // [(P + 15) / 16][workgroups of a full block][16]
@@ -2772,6 +2824,7 @@ void wb_scan_free(WbScan *s) {
   if (s->d_partial) hipFree(s->d_partial);
   if (s->d_clip) hipFree(s->d_clip);
   if (s->d_sm) hipFree(s->d_sm);
+  iqc_free(s->iqc);
   delete s;
 }
 } // namespace
@@ -2802,6 +2855,8 @@ int fmx_wb_scan_create(void *handle, const fmx_wb_scan_config *cfg, void **scan)
   const size_t row = static_cast<size_t>(4) * p.Lp;
   std::vector<uint16_t> rows(row * s->P);
   for (int k = 0; k < s->P; ++k) wb_weight_rows(p, cfg->start_hz + k * cfg->step_hz, rows.data() + row * k);
+  s->iqc.tsum.resize(static_cast<size_t>(2) * s->P);
+  for (int k = 0; k < s->P; ++k) wb_tap_sums(p, rows.data() + row * k, s->iqc.tsum.data() + 2 * k);
   const size_t n_partial = static_cast<size_t>((s->P + 15) / 16) * wb_scan_workgroups(p.block, p.tpp, nt) * 16;
   const size_t n_clip = static_cast<size_t>(wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D)) * 2;
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->d_w), rows.size() * sizeof(uint16_t));
@@ -2891,11 +2946,139 @@ int fmx_wb_scan_process(void *scan, const void *d_wide, int n_out, fmx_signal_le
   // raw integers (2 b - 255 for u8) times weights * 2^sexp, squared
   a.pscale = std::ldexp(a.s16 ? std::ldexp(1.0, -30) : 1.0 / (255.0 * 255.0), -2 * p.sexp);
   for (int k = 0; k < 4; ++k) a.sp[k] = s->sp[k];
-  if ((rc = launch_wb_scan(a, h->sA)) != FMX_OK) {
+  if (s->iqc.mode == FMX_IQC_OFF) {
+    rc = launch_wb_scan(a, h->sA);
+  } else { // estimator, finisher, corrected scan
+    rc = FMX_OK;
+    if (s->iqc.mode == FMX_IQC_AUTO)
+      rc = launch_iqc_estimate(d_wide, static_cast<long>(n_out) * p.D, a.s16, s->iqc.alpha, s->iqc.d_partial, s->iqc.d_blk,
+                               h->sA);
+    if (rc == FMX_OK) rc = launch_wb_scan_iqc(a, s->iqc.d_blk, s->iqc.d_tsum, h->sA);
+  }
+  if (rc != FMX_OK) {
     h->err = "fmx_wb_scan_process: kernel launch failed";
     return rc;
   }
   return FMX_OK;
+}
+
+/* ---- DC offset and IQ imbalance (fmx.h; kernels in fmx_wb_iqc.inc) ---- */
+namespace {
+// The mode of one object's Iqc: validates, allocates on the first mode other
+// than OFF, and queues the block's rewrite on sA (behind the calls queued so
+// far, ahead of later ones).
+int iqc_set(Handle *h, Iqc &q, const WbPlan &p, const char *who, int mode, const fmx_iq_correction *fixed, double alpha) {
+  const char *bad = nullptr;
+  if (mode != FMX_IQC_OFF && mode != FMX_IQC_FIXED && mode != FMX_IQC_AUTO) bad = "unknown mode";
+  else if (mode == FMX_IQC_FIXED && !fixed) bad = "FMX_IQC_FIXED needs the parameters";
+  else if (mode == FMX_IQC_FIXED && !(std::isfinite(fixed->dc_i) && std::isfinite(fixed->dc_q) &&
+                                      std::isfinite(fixed->gain) && std::isfinite(fixed->cross)))
+    bad = "a parameter is not finite";
+  else if (mode == FMX_IQC_FIXED && !(fixed->gain > 0.0)) bad = "gain must be positive";
+  else if (mode == FMX_IQC_AUTO && !(alpha >= 0.0 && alpha <= 1.0)) bad = "alpha must lie in (0, 1] (0: 1 / 16)";
+  if (bad) {
+    h->err = std::string(who) + ": " + bad;
+    return FMX_E_INVALID;
+  }
+  if (mode == FMX_IQC_OFF) {
+    q.mode = mode;
+    return FMX_OK;
+  }
+  const int s16 = p.format == FMX_WB_S16;
+  if (!q.d_blk) {
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n_partial = static_cast<size_t>(iqc_workgroups(static_cast<long>(p.block) * p.D, s16)) * 5;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&q.d_blk), sizeof(FmxIqcBlock));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&q.d_partial), n_partial * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&q.d_tsum), q.tsum.size() * sizeof(float));
+    // synchronous: the table is complete before a corrected call is queued
+    // (fmx_wb_set_freq keeps it current from here on)
+    if (e == hipSuccess) e = hipMemcpy(q.d_tsum, q.tsum.data(), q.tsum.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      iqc_free(q);
+      q.mode = FMX_IQC_OFF;
+      h->err = std::string(who) + ": " + hipGetErrorString(e);
+      return FMX_E_NOMEM;
+    }
+  }
+  FmxIqcBlock v{}; // AUTO: identity until the first call's estimate; init = 0 restarts the smoothing
+  v.x = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
+  if (mode == FMX_IQC_FIXED) v.x = *fixed;
+  const double unit = s16 ? 32768.0 : 255.0;
+  v.k[0] = static_cast<float>(v.x.dc_i * unit);
+  v.k[1] = static_cast<float>(v.x.dc_q * unit);
+  v.k[2] = static_cast<float>(v.x.gain);
+  v.k[3] = static_cast<float>(v.x.cross);
+  int rc;
+  if ((rc = launch_iqc_set(q.d_blk, v, h->sA)) != FMX_OK) {
+    h->err = std::string(who) + ": kernel launch failed";
+    return rc;
+  }
+  q.mode = mode;
+  q.alpha = alpha == 0.0 ? 1.0 / 16.0 : alpha;
+  return FMX_OK;
+}
+int iqc_get(Handle *h, const Iqc &q, const char *who, fmx_iq_correction *h_out) {
+  if (!h_out) {
+    h->err = std::string(who) + ": null h_out";
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->sA));
+  if (q.mode == FMX_IQC_OFF) {
+    *h_out = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
+    return FMX_OK;
+  }
+  FmxIqcBlock b;
+  HIP_TRY(hipMemcpy(&b, q.d_blk, sizeof(b), hipMemcpyDeviceToHost));
+  *h_out = b.x;
+  return FMX_OK;
+}
+// the object behind a fmx_wb_*iq_correction call, or NULL with the handle's message set
+Wb *iqc_wb(void *wb, const char *who) {
+  Wb *w = W(wb);
+  if (!w) return nullptr;
+  const char *bad = nullptr;
+  if (w->kind == WB_KIND_BANK) bad = "the capture bank has no IQ correction (out of scope)";
+  else if (w->kind != WB_KIND_WB) bad = "not an fmx_wb object";
+  else if (w->rational) bad = "an object of fmx_wb_create_rational at Q > 1 has no IQ correction (out of scope)";
+  if (bad) {
+    w->h->err = std::string(who) + ": " + bad;
+    return nullptr;
+  }
+  return w;
+}
+WbScan *iqc_scan(void *scan, const char *who) {
+  WbScan *s = WS(scan);
+  if (!s) return nullptr;
+  if (s->kind != WB_KIND_SCAN) {
+    s->h->err = std::string(who) + (s->kind == WB_KIND_BANK ? ": the capture bank has no IQ correction (out of scope)"
+                                                            : ": not an fmx_wb_scan object");
+    return nullptr;
+  }
+  return s;
+}
+} // namespace
+
+int fmx_wb_set_iq_correction(void *wb, int mode, const fmx_iq_correction *fixed, double alpha) {
+  Wb *w = iqc_wb(wb, "fmx_wb_set_iq_correction");
+  if (!w) return FMX_E_INVALID;
+  return iqc_set(w->h, w->iqc, w->p, "fmx_wb_set_iq_correction", mode, fixed, alpha);
+}
+int fmx_wb_iq_correction(void *wb, fmx_iq_correction *h_out) {
+  Wb *w = iqc_wb(wb, "fmx_wb_iq_correction");
+  if (!w) return FMX_E_INVALID;
+  return iqc_get(w->h, w->iqc, "fmx_wb_iq_correction", h_out);
+}
+int fmx_wb_scan_set_iq_correction(void *scan, int mode, const fmx_iq_correction *fixed, double alpha) {
+  WbScan *s = iqc_scan(scan, "fmx_wb_scan_set_iq_correction");
+  if (!s) return FMX_E_INVALID;
+  return iqc_set(s->h, s->iqc, s->p, "fmx_wb_scan_set_iq_correction", mode, fixed, alpha);
+}
+int fmx_wb_scan_iq_correction(void *scan, fmx_iq_correction *h_out) {
+  WbScan *s = iqc_scan(scan, "fmx_wb_scan_iq_correction");
+  if (!s) return FMX_E_INVALID;
+  return iqc_get(s->h, s->iqc, "fmx_wb_scan_iq_correction", h_out);
 }
 
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes) {

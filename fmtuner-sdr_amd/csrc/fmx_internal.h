@@ -9,6 +9,7 @@
 
 #include "../../include/fmx.h"
 #include "fmx_design.h"
+#include "fmx_iqc.h"
 
 namespace fmx {
 
@@ -423,6 +424,17 @@ struct WbLevelArgs {
   long n_in;               // the call's raw samples when they are not n * D (a rational object: n P / Q; D is then unused); 0: n * D
 };
 int launch_wb_level(const WbLevelArgs &a, void *stream);
+
+// ---- DC offset and IQ imbalance (fmx_iqc.h, fmx_wb_iqc.inc) ----
+// (SR, SI) of one channel's rows: the sums of its taps as the kernel multiplies them (units of W * 2^sexp)
+void wb_tap_sums(const WbPlan &p, const uint16_t *rows, float *out2);
+int iqc_workgroups(long n_in, int s16);                                  // k_iqc_sums' grid: [workgroups][5] int64 partials
+int launch_iqc_set(FmxIqcBlock *blk, const FmxIqcBlock &v, void *stream); // the whole block (FIXED, or AUTO's restart)
+// the estimator and its finisher over one call's raw samples: the block holds the call's parameters behind them
+int launch_iqc_estimate(const void *in, long n_in, int s16, double alpha, long long *partial, FmxIqcBlock *blk, void *stream);
+// launch_wb / launch_wb_scan with the corrected kernels; tsum: [C][2] / [P][2] tap sums (device)
+int launch_wb_iqc(const WbArgs &a, const FmxIqcBlock *iqc, const float *tsum, void *stream);
+int launch_wb_scan_iqc(const WbScanArgs &a, const FmxIqcBlock *iqc, const float *tsum, void *stream);
 
 // ---- capture bank (fmx_wb_bank.inc): S captures of one plan channelized by one launch ----
 #define FMX_WBB_CAPTURES_MAX 1024

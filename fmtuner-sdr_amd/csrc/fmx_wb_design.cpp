@@ -116,6 +116,20 @@ void wb_rows_to_taps(const WbPlan &p, const uint16_t *rows, float *out) {
   }
 }
 
+// SR + j SI = sum_k W[k] of one channel, from the rows the kernel multiplies
+// (hi + lo of every entry, units of W * 2^sexp): the corrected kernels'
+// per-channel DC constant
+void wb_tap_sums(const WbPlan &p, const uint16_t *rows, float *out2) {
+  for (int c = 0; c < 2; ++c) {
+    double s = 0.0;
+    for (int k = 0; k < p.L; ++k) {
+      const int kk = p.Lp - 1 - k;
+      s += wb_f16_value(rows[(2 * c) * p.Lp + kk]) + wb_f16_value(rows[(2 * c + 1) * p.Lp + kk]);
+    }
+    out2[c] = static_cast<float>(s);
+  }
+}
+
 // ---- rational rates ----
 // wide_rate / dsp_rate = P / Q in lowest terms.  The prototype is designed at
 // the up-sampled rate Q Fs: Lup = P tpp taps, fc = min(0.45 / P, 0.45), gain
@@ -292,6 +306,30 @@ extern "C" int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int mi
     ++count;
   }
   return count;
+}
+
+extern "C" int fmx_iq_estimate(const void *h_raw, int format, long n_samples, fmx_iq_correction *out) {
+  if (!h_raw || !out || n_samples <= 0 || (format != FMX_WB_U8 && format != FMX_WB_S16)) return FMX_E_INVALID;
+  long long s[5] = {0, 0, 0, 0, 0};
+  for (long i = 0; i < n_samples; ++i) {
+    long long vi, vq;
+    if (format == FMX_WB_S16) {
+      vi = static_cast<const int16_t *>(h_raw)[2 * i];
+      vq = static_cast<const int16_t *>(h_raw)[2 * i + 1];
+    } else {
+      vi = 2 * static_cast<int>(static_cast<const uint8_t *>(h_raw)[2 * i]) - 255;
+      vq = 2 * static_cast<int>(static_cast<const uint8_t *>(h_raw)[2 * i + 1]) - 255;
+    }
+    s[0] += vi;
+    s[1] += vq;
+    s[2] += vi * vi;
+    s[3] += vq * vq;
+    s[4] += vi * vq;
+  }
+  FmxIqcBlock b{};
+  fmx_iqc_finish(s, n_samples, 1.0, format == FMX_WB_S16 ? 32768.0 : 255.0, &b);
+  *out = b.x;
+  return FMX_OK;
 }
 
 extern "C" int fmx_wb_ratio(const fmx_wb_config *cfg, int *P, int *Q, int *taps) {

@@ -75,6 +75,17 @@ class WbScanConfig(C.Structure):
     _fields_ = [("wb", WbConfig), ("start_hz", C.c_int), ("step_hz", C.c_int), ("n_points", C.c_int)]
 
 
+FMX_IQC_OFF, FMX_IQC_FIXED, FMX_IQC_AUTO = 0, 1, 2
+
+
+class IqCorrection(C.Structure):
+    """fmx_iq_correction: x' = (I - dc_i) + j (gain (Q - dc_q) + cross (I - dc_i)), units of x."""
+    _fields_ = [(n, C.c_double) for n in ("dc_i", "dc_q", "gain", "cross")]
+
+    def astuple(self):
+        return (self.dc_i, self.dc_q, self.gain, self.cross)
+
+
 _lib = None
 _OPTIONAL = {"fmx_build_info", "fmx_host_stats", "fmx_diag_set", "fmx_diag_rds_ring"}  # absent from older libraries (A/B against past revisions)
 
@@ -141,6 +152,11 @@ def lib():
         "fmx_wb_scan_process": (i, [vp, vp, i, vp]),
         "fmx_wb_scan_points": (i, [C.POINTER(WbScanConfig), C.POINTER(i), i]),
         "fmx_scan_peaks": (i, [C.POINTER(C.c_double), i, C.c_double, i, C.POINTER(i), i]),
+        "fmx_wb_set_iq_correction": (i, [vp, i, C.POINTER(IqCorrection), C.c_double]),
+        "fmx_wb_iq_correction": (i, [vp, C.POINTER(IqCorrection)]),
+        "fmx_wb_scan_set_iq_correction": (i, [vp, i, C.POINTER(IqCorrection), C.c_double]),
+        "fmx_wb_scan_iq_correction": (i, [vp, C.POINTER(IqCorrection)]),
+        "fmx_iq_estimate": (i, [vp, i, C.c_long, C.POINTER(IqCorrection)]),
         "fmx_malloc": (i, [vp, C.POINTER(vp), sz]),
         "fmx_free": (i, [vp, vp]),
         "fmx_memcpy_h2d": (i, [vp, vp, vp, sz]),
@@ -399,6 +415,37 @@ class Wideband:
         """Restarts one channel's level smoother (-1: every channel's)."""
         self._ck(self.L.fmx_wb_signal_reset(self.w, channel), "fmx_wb_signal_reset")
 
+    def set_iq_correction(self, mode, fixed=None, alpha=0.0):
+        """fmx_wb_set_iq_correction: FMX_IQC_OFF, FMX_IQC_FIXED (fixed: an
+        IqCorrection or (dc_i, dc_q, gain, cross)) or FMX_IQC_AUTO (alpha in
+        (0, 1], 0: 1 / 16); holds from the next process call on."""
+        self._ck(self.L.fmx_wb_set_iq_correction(self.w, mode, _iq_fixed(fixed), alpha), "fmx_wb_set_iq_correction")
+
+    def iq_correction(self):
+        """fmx_wb_iq_correction: waits for the queued calls; (dc_i, dc_q, gain, cross) as of the last one."""
+        out = IqCorrection()
+        self._ck(self.L.fmx_wb_iq_correction(self.w, C.byref(out)), "fmx_wb_iq_correction")
+        return out.astuple()
+
+
+def _iq_fixed(fixed):
+    if fixed is None or isinstance(fixed, IqCorrection):
+        return fixed
+    return IqCorrection(*[float(v) for v in fixed])
+
+
+def iq_estimate(raw, format):
+    """fmx_iq_estimate (host only): the estimator of one buffer of interleaved
+    raw I/Q (numpy uint8 for FMX_WB_U8, int16 for FMX_WB_S16), no smoothing
+    -> (dc_i, dc_q, gain, cross)."""
+    import numpy as np
+    raw = np.ascontiguousarray(raw, dtype=np.int16 if format == FMX_WB_S16 else np.uint8)
+    out = IqCorrection()
+    rc = lib().fmx_iq_estimate(raw.ctypes.data_as(C.c_void_p), format, raw.size // 2, C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(f"fmx_iq_estimate failed ({rc})")
+    return out.astuple()
+
 
 class WidebandBank:
     """The capture bank of one Handle (fmx_wb_bank_*): len(freq_hz) wide
@@ -579,6 +626,16 @@ class WidebandScan:
         """d_wide: n_out * D interleaved I/Q samples; d_level: [n_points] fmx_signal_level (40 bytes each)."""
         self._ck(self.L.fmx_wb_scan_process(self.s, C.c_void_p(d_wide), n_out, C.c_void_p(d_level)),
                  "fmx_wb_scan_process")
+
+    def set_iq_correction(self, mode, fixed=None, alpha=0.0):
+        """fmx_wb_scan_set_iq_correction: as Wideband.set_iq_correction, for the reads from the next one on."""
+        self._ck(self.L.fmx_wb_scan_set_iq_correction(self.s, mode, _iq_fixed(fixed), alpha),
+                 "fmx_wb_scan_set_iq_correction")
+
+    def iq_correction(self):
+        out = IqCorrection()
+        self._ck(self.L.fmx_wb_scan_iq_correction(self.s, C.byref(out)), "fmx_wb_scan_iq_correction")
+        return out.astuple()
 
 
 def wb_scan_points(scfg):

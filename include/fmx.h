@@ -47,7 +47,9 @@
 extern "C" {
 #endif
 
-/* ABI history: rational wide rates (fmx_wb_create_rational, fmx_wb_ratio, fmx_wb_weights_rational,
+/* ABI history: the DC / IQ-imbalance correction (fmx_wb_set_iq_correction, fmx_wb_iq_correction,
+ * fmx_wb_scan_set_iq_correction, fmx_wb_scan_iq_correction, fmx_iq_estimate, fmx_iq_correction, FMX_IQC_*)
+ * arrived at 13 without a bump, as the bank and the rational rates did: additions only; rational wide rates (fmx_wb_create_rational, fmx_wb_ratio, fmx_wb_weights_rational,
  * fmx_wb_rational_geometry: 20, 10 and 2.048 MS/s captures channelized at P / Q) arrived at 13 without a bump,
  * as the bank did: additions only; the capture bank (fmx_wb_bank_*: many wide captures channelized in one call) arrived at 13
  * without a bump: its symbols are additions, no existing symbol, struct or enum changed, and a caller built
@@ -475,6 +477,64 @@ int fmx_wb_scan_points(const fmx_wb_scan_config *cfg, int *freq_hz, int cap);
  * (a tie goes to the lowest index).  Writes the first min(cap, count) indices,
  * ascending; returns the count (negative on error). */
 int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int min_spacing, int *idx, int cap);
+
+/* ---- DC offset and IQ imbalance of a wide capture ----
+ * A zero-IF front end adds a DC offset (a carrier at the capture's centre)
+ * and mismatches its I and Q paths in gain and phase (every station at +f
+ * mirrored to -f, 25 to 40 dB down).  With x = I + jQ the normalised sample
+ * as fmx_wb_process defines it, the corrected sample is
+ *   x' = (I - dc_i) + j (gain (Q - dc_q) + cross (I - dc_i))
+ * and every output of a call -- rows, and through them fmx_wb_process_block's
+ * audio and RDS, fmx_wb_signal's levels, the scan's records -- is the
+ * channelizer's formula on x', with the parameters in force for THAT CALL over
+ * its whole window, history samples included (the history is kept raw).
+ * Before the stream's start x is 0 as without correction, and the correction
+ * applies to those zeros too (x' = C(0)).  The clip ratios stay those of the
+ * raw samples.  Identity parameters (0, 0, 1, 0) give the uncorrected rows as
+ * numbers.
+ *   FMX_IQC_OFF    (default) no correction: the object launches the kernels
+ *                  it launched before this call existed
+ *   FMX_IQC_FIXED  the caller's parameters
+ *   FMX_IQC_AUTO   estimated on the GPU from each call's own raw samples (the
+ *                  estimate is in force for the call it was taken from), with
+ *                  no host synchronisation
+ * In OFF and FIXED the rows do not depend on how the stream is cut into
+ * calls; in AUTO they DO, because the parameters change with every call.
+ * Estimator: with v the raw value (2 b - 255 for u8, v for int16), the sums
+ * of I, Q, I^2, Q^2 and IQ over the call's raw samples are formed as 64-bit
+ * integers (exact: no summation order matters) and divided by the sample
+ * count; each of the five moments is smoothed across calls, m <- m + alpha
+ * (m_call - m), the first call after the mode was set initialising m; with
+ * mI, mQ and the central moments cII, cQQ, cIQ of m,
+ *   v = cQQ - cIQ^2 / cII,  gain = sqrt(cII / v),  cross = -gain cIQ / cII,
+ *   dc = (mI, mQ) in units of x
+ * (Gram-Schmidt: Q' has I's power and no correlation with it).  If !(cII > 0)
+ * or !(v > 1e-9 cQQ), gain = 1 and cross = 0; dc still applies.  alpha must
+ * lie in (0, 1] for AUTO; 0 selects 1 / 16 (a design choice -- about 16 calls
+ * of memory -- not a measurement).  `fixed` is needed for FIXED and ignored
+ * otherwise.  The call is ordered on the stage stream and holds from the next
+ * process call on; setting a mode again restarts the estimate; fmx_wb_reset
+ * and fmx_wb_set_freq leave it alone (it is a property of the hardware).  The
+ * scan treats each read independently as before; only the smoothed moments
+ * carry over between reads.  FMX_E_INVALID (message naming the function) for
+ * a bad mode, an alpha outside the range, a NULL `fixed` in FIXED, a
+ * non-finite field or gain <= 0.  Out of scope, FMX_E_INVALID as well: an
+ * object made by fmx_wb_create_rational at Q > 1 (19.2 and 24 MS/s are
+ * integer rates) and the capture bank; frequency-dependent imbalance is not
+ * modelled.  fmx_wb_iq_correction / fmx_wb_scan_iq_correction wait for the
+ * queued calls and return the parameters as of the last one (identity in OFF).
+ * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
+typedef struct { double dc_i, dc_q, gain, cross; } fmx_iq_correction; /* units of x */
+enum { FMX_IQC_OFF = 0, FMX_IQC_FIXED = 1, FMX_IQC_AUTO = 2 };
+int fmx_wb_set_iq_correction(void *wb, int mode, const fmx_iq_correction *fixed, double alpha);
+int fmx_wb_iq_correction(void *wb, fmx_iq_correction *h_out);
+int fmx_wb_scan_set_iq_correction(void *scan, int mode, const fmx_iq_correction *fixed, double alpha);
+int fmx_wb_scan_iq_correction(void *scan, fmx_iq_correction *h_out);
+/* host only, no GPU: the estimator of one buffer of n_samples interleaved raw
+ * I/Q pairs (format FMX_WB_*), without smoothing: the formula a caller or a
+ * test can check against.  FMX_E_INVALID for n_samples <= 0, a NULL argument
+ * or an unknown format. */
+int fmx_iq_estimate(const void *h_raw, int format, long n_samples, fmx_iq_correction *out);
 
 /* ---- device memory helpers (so C/FFI callers need no HIP headers) ---- */
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes);

@@ -334,7 +334,7 @@ int launch_wb(const WbArgs &a, void *stream);
 // decimation P whose outputs interleave.  Output n = Q m + r ends at wide
 // sample i0 = m P + a_r and uses the taps h[Q j + b_r], r P = Q a_r + b_r.
 #define FMX_WBR_QMAX 16
-constexpr int kWbLdsMax = 80 * 1024; // WB_LDS_MAX (fmx_wb.inc)
+constexpr int kWbLdsMax = 80 * 1024; // WB_LDS_MAX (fmx_wb_core.inc)
 constexpr int kWbNtMax = 16;         // WB_NT_MAX
 struct WbrPlan {
   int P = 0, Q = 0, tpp = 0, Lup = 0, Lp = 0; // Lp: the largest L_r rounded up to the MFMA's K = 32

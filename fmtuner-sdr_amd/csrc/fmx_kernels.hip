@@ -3886,6 +3886,7 @@ int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sa
                      n_samples, bits, out, out_stride);
   return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
 }
+#include "fmx_wb_core.inc"
 #include "fmx_wb.inc"
 #include "fmx_wb_scan.inc"
 #include "fmx_wb_level.inc"

@@ -6,19 +6,17 @@
  * bank and row s of the call's input [S][wide_stride].  The kernel's work is
  * a flat device table of groups {capture, first channel, channels 1..16}
  * (fmx_wb_bank_groups): one entry per 16 channels of a capture, none for an
- * empty capture, blockIdx.y its index.  k_wbb is k_wb's body, statement for
- * statement and in k_wb's order -- the same LDS images, the same four chains
- * with hi*hi, hi*lo, lo*hi per K step, the same rotation and store -- with
- * in, hist, valid and base_mod taken from the group's capture, so a capture's
- * rows are bit for bit those of an fmx_wb object fed its row.  It is a copy
- * and not a parameter of k_wb: k_wb's assembly stays what it was.
+ * empty capture, blockIdx.y its index.  k_wbb is k_wb's use of the shared
+ * pieces (fmx_wb_core.inc) with in, hist, valid and base_mod taken from the
+ * group's capture and the channels from the group; the image, the chains and
+ * the rotation are the one definition k_wb runs, so a capture's rows are bit
+ * for bit those of an fmx_wb object fed its row.
  * Each capture's {counter, valid} lives on the device (WbbState): k_wbb reads
  * it, k_wbb_hist (one writer per capture, behind k_wbb on the stream)
  * advances it, k_wbb_set_state rewrites it for a reset -- calls, resets and
  * parameter changes stay queued with no host synchronisation and no staging
  * image that would have to outlive the call. */
 template <bool S16, bool EVEN> __global__ __launch_bounds__(256) void k_wbb(WbbArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wbb_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the workgroup's group and its capture
   const int *grp = a.groups + 3 * (size_t)blockIdx.y;
@@ -31,93 +29,17 @@ template <bool S16, bool EVEN> __global__ __launch_bounds__(256) void k_wbb(WbbA
   const int n0 = (int)blockIdx.x * 16 * a.nt; // first output of the workgroup
   const int NI = (16 * a.nt - 1) * a.D + a.Lp; // samples of the window
   const int NIp = (NI + 7) & ~7;
-  _Float16 *ih = reinterpret_cast<_Float16 *>(wbb_smem);
-  _Float16 *qh = ih + NIp, *il = qh + NIp, *ql = il + NIp; // il, ql: s16 only
-  // image entry idx = wide sample a0 + idx of this call (negative: the history)
-  const long a0 = (long)n0 * a.D - (a.Lp - 1);
-  const long n_in = (long)a.n_out * a.D;
-  for (int idx = tid; idx < NIp; idx += 256) {
-    const long i = a0 + idx;
-    int vi = 0, vq = 0; // before the stream's start and past the call's input: zeros
-    if (idx < NI && i >= -(long)valid && i < n_in) {
-      if (S16) {
-        const int16_t *src = i < 0 ? reinterpret_cast<const int16_t *>(chist) + 2 * (a.L - 1 + i)
-                                   : reinterpret_cast<const int16_t *>(cin) + 2 * i;
-        if (i < 0 || a.in_al) {
-          const uint32_t v = *reinterpret_cast<const uint32_t *>(src);
-          vi = (int16_t)(v & 0xFFFFu);
-          vq = (int16_t)(v >> 16);
-        } else {
-          vi = src[0];
-          vq = src[1];
-        }
-      } else {
-        const uint8_t *src = i < 0 ? reinterpret_cast<const uint8_t *>(chist) + 2 * (a.L - 1 + i)
-                                   : reinterpret_cast<const uint8_t *>(cin) + 2 * i;
-        uint32_t bi, bq;
-        if (i < 0 || a.in_al) {
-          const uint32_t v = *reinterpret_cast<const uint16_t *>(src);
-          bi = v & 0xFFu;
-          bq = v >> 8;
-        } else {
-          bi = src[0];
-          bq = src[1];
-        }
-        vi = 2 * (int)bi - 255;
-        vq = 2 * (int)bq - 255;
-      }
-    }
-    const float fi = (float)vi, fq = (float)vq;
-    const _Float16 hi = (_Float16)fi, hq = (_Float16)fq;
-    ih[idx] = hi;
-    qh[idx] = hq;
-    if (S16) { // |v - hi| <= 8: exact
-      il[idx] = (_Float16)(fi - (float)hi);
-      ql[idx] = (_Float16)(fq - (float)hq);
-    }
-  }
-  __syncthreads();
+  const WbImage m = wb_image(NIp);
+  wb_stage<S16, true>(m, NI, NIp, (long)n0 * a.D - (a.Lp - 1), (long)a.n_out * a.D, valid, cin, chist, a.L, a.in_al, tid);
   const int col = lane & 15, g = lane >> 4;
-  const int KS = a.Lp >> 5;
   // a ragged group computes its last channel again in the spare rows (not stored)
   const int ca = c0 + min(col, cn - 1);
   const uint16_t *wrow = a.w + (size_t)ca * 4 * a.Lp + 8 * g;
-  auto wld = [&](int ks, int part) __attribute__((always_inline)) {
-    return *reinterpret_cast<const wb_u32x4 *>(wrow + (size_t)part * a.Lp + 32 * ks);
-  };
   for (int t = wave; t < a.nt; t += 4) {
     const int nt0 = n0 + 16 * t;
     if (nt0 >= a.n_out) break;
-    const int xb = (16 * t + col) * a.D + 8 * g;
-    wb_f32x4 rr = {0.0f, 0.0f, 0.0f, 0.0f}, ii = rr, ri = rr, ir = rr;
-    wb_u32x4 n_rh = wld(0, 0), n_rl = wld(0, 1), n_ih = wld(0, 2), n_il = wld(0, 3);
-    for (int ks = 0; ks < KS; ++ks) {
-      const wb_f16x8 wrh = __builtin_bit_cast(wb_f16x8, n_rh), wrl = __builtin_bit_cast(wb_f16x8, n_rl);
-      const wb_f16x8 wih = __builtin_bit_cast(wb_f16x8, n_ih), wil = __builtin_bit_cast(wb_f16x8, n_il);
-      if (ks + 1 < KS) {
-        n_rh = wld(ks + 1, 0);
-        n_rl = wld(ks + 1, 1);
-        n_ih = wld(ks + 1, 2);
-        n_il = wld(ks + 1, 3);
-      }
-      const int x = xb + 32 * ks;
-      const wb_f16x8 xih = wb_frag<EVEN>(ih + x), xqh = wb_frag<EVEN>(qh + x);
-      rr = __builtin_amdgcn_mfma_f32_16x16x32_f16(wrh, xih, rr, 0, 0, 0);
-      ii = __builtin_amdgcn_mfma_f32_16x16x32_f16(wih, xqh, ii, 0, 0, 0);
-      ri = __builtin_amdgcn_mfma_f32_16x16x32_f16(wrh, xqh, ri, 0, 0, 0);
-      ir = __builtin_amdgcn_mfma_f32_16x16x32_f16(wih, xih, ir, 0, 0, 0);
-      if (S16) {
-        const wb_f16x8 xil = wb_frag<EVEN>(il + x), xql = wb_frag<EVEN>(ql + x);
-        rr = __builtin_amdgcn_mfma_f32_16x16x32_f16(wrh, xil, rr, 0, 0, 0);
-        ii = __builtin_amdgcn_mfma_f32_16x16x32_f16(wih, xql, ii, 0, 0, 0);
-        ri = __builtin_amdgcn_mfma_f32_16x16x32_f16(wrh, xql, ri, 0, 0, 0);
-        ir = __builtin_amdgcn_mfma_f32_16x16x32_f16(wih, xil, ir, 0, 0, 0);
-      }
-      rr = __builtin_amdgcn_mfma_f32_16x16x32_f16(wrl, xih, rr, 0, 0, 0);
-      ii = __builtin_amdgcn_mfma_f32_16x16x32_f16(wil, xqh, ii, 0, 0, 0);
-      ri = __builtin_amdgcn_mfma_f32_16x16x32_f16(wrl, xqh, ri, 0, 0, 0);
-      ir = __builtin_amdgcn_mfma_f32_16x16x32_f16(wil, xih, ir, 0, 0, 0);
-    }
+    wb_f32x4 rr, ii, ri, ir;
+    wb_tile<S16, EVEN>(m, (16 * t + col) * a.D + 8 * g, wrow, a.Lp, rr, ii, ri, ir);
     // lane: output nt0 + col of the group's channels 4 g + i
     const int n = nt0 + col;
     if (n >= a.n_out) continue;
@@ -126,25 +48,8 @@ template <bool S16, bool EVEN> __global__ __launch_bounds__(256) void k_wbb(WbbA
     for (int i = 0; i < 4; ++i) {
       if (4 * g + i >= cn) break;
       const int c = c0 + 4 * g + i;
-      const uint64_t p = ((uint64_t)a.fpos[c] * smod) % a.fs; // theta = p / Fs turns
-      const double turns = (double)p * a.inv_fs;
-      const int quad = (int)(4.0 * turns + 0.5); // 0..4
-      const float r = (float)(turns - 0.25 * (double)quad); // |r| <= 1/8 turn
-      float sn, cs;
-      sincospif(2.0f * r, &sn, &cs);
-      if (quad & 1) { // a quarter turn more: (cos, sin) -> (-sin, cos)
-        const float tmp = cs;
-        cs = -sn;
-        sn = tmp;
-      }
-      if (quad & 2) {
-        cs = -cs;
-        sn = -sn;
-      }
-      const float re = rr[i] - ii[i], im = ri[i] + ir[i];
-      float *po = a.out + 2 * ((size_t)c * a.out_stride + n);
-      po[0] = (re * cs + im * sn) * a.scale; // (re + j im) e^{-j theta}
-      po[1] = (im * cs - re * sn) * a.scale;
+      wb_rotate_store(a.fpos[c], smod, a.fs, a.inv_fs, rr[i] - ii[i], ri[i] + ir[i], a.scale,
+                      a.out + 2 * ((size_t)c * a.out_stride + n));
     }
   }
 }
@@ -193,18 +98,6 @@ __global__ void k_wbb_set_params(double *sp, int S, int capture, double v0, doub
   }
 }
 
-template <bool S16, bool EVEN> static int wbb_launch(const WbbArgs &a, size_t smem, dim3 grid, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wbb<S16, EVEN>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, WB_LDS_MAX) != hipSuccess)
-      return FMX_E_HIP;
-    configured = true;
-  }
-  hipLaunchKernelGGL((k_wbb<S16, EVEN>), grid, dim3(256), smem, st, a);
-  return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
-}
-
 int launch_wbb(const WbbArgs &a0, void *stream) {
   WbbArgs a = a0;
   if (a.S <= 0 || a.n_out <= 0) return FMX_OK;
@@ -212,26 +105,15 @@ int launch_wbb(const WbbArgs &a0, void *stream) {
       a.wide_stride < (size_t)a.n_out * (size_t)a.D)
     return FMX_E_INVALID;
   if (a.D < 2 || a.L != (a.L / a.D) * a.D || a.Lp < a.L || (a.Lp & 31)) return FMX_E_INVALID;
-  // wb_tiles and launch_wb's LDS size: the tiling is the single object's
-  WbArgs t{};
-  t.s16 = a.s16;
-  t.D = a.D;
-  t.Lp = a.Lp;
-  t.n_out = a.n_out;
-  a.nt = wb_tiles(t);
+  a.nt = wb_tiles(a.D, a.Lp, a.s16, a.n_out); // the tiling is the single object's
   if (a.nt < 1) return FMX_E_INVALID;
-  const uintptr_t al = a.s16 ? 3 : 1; // every row starts a whole number of samples behind the base
-  a.in_al = (reinterpret_cast<uintptr_t>(a.in) & al) == 0;
-  const int NI = (16 * a.nt - 1) * a.D + a.Lp;
-  const size_t smem = (size_t)((NI + 7) & ~7) * (a.s16 ? 8 : 4);
+  a.in_al = wb_in_aligned(a.in, a.s16); // every row starts a whole number of samples behind the base
+  const size_t smem = wb_lds_bytes((16 * a.nt - 1) * a.D + a.Lp, a.s16);
   if (smem > WB_LDS_MAX) return FMX_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.G > 0) {
     const dim3 grid((unsigned)((a.n_out + 16 * a.nt - 1) / (16 * a.nt)), (unsigned)a.G);
-    const bool even = (a.D & 1) == 0;
-    int rc;
-    if (a.s16) rc = even ? wbb_launch<true, true>(a, smem, grid, st) : wbb_launch<true, false>(a, smem, grid, st);
-    else rc = even ? wbb_launch<false, true>(a, smem, grid, st) : wbb_launch<false, false>(a, smem, grid, st);
+    const int rc = WB_LAUNCH(k_wbb, a.s16, (a.D & 1) == 0, grid, smem, st, a);
     if (rc != FMX_OK) return rc;
   }
   const dim3 hgrid((unsigned)((a.L - 1 + 255) / 256), (unsigned)a.S);
@@ -254,118 +136,21 @@ int launch_wbb_set_params(double *sp, int S, int capture, const double *v, void 
 }
 
 /* ---- the bank's RF level (fmx_wb_bank_signal): k_wb_scan_clip and k_wb_level with a capture dimension ---- */
-// k_wb_scan_clip's counting, the same 2048 samples per workgroup, over row
-// blockIdx.y of the call's input: the counts to clip[capture][workgroup][2]
+// the same 2048 samples per workgroup over row blockIdx.y of the call's input:
+// the counts to clip[capture][workgroup][2]
 template <typename T> __global__ __launch_bounds__(256) void k_wbb_clip(WbbLevelArgs a) {
-  __shared__ uint32_t red[4][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long n_in = (long)a.n * a.D;
-  const T *in = static_cast<const T *>(a.in) + 2 * (size_t)blockIdx.y * a.wide_stride;
-  uint32_t hard = 0, nearc = 0;
-  for (int k = 0; k < 8; ++k) {
-    const long i = (long)blockIdx.x * 2048 + 256 * k + tid;
-    if (i >= n_in) break;
-    uint32_t bi, bq;
-    if (sizeof(T) == 2) {
-      bi = (uint32_t)(((int)in[2 * i] >> 8) + 128);
-      bq = (uint32_t)(((int)in[2 * i + 1] >> 8) + 128);
-    } else {
-      bi = (uint32_t)in[2 * i];
-      bq = (uint32_t)in[2 * i + 1];
-    }
-    const uint32_t lo = min(bi, bq), hi = max(bi, bq);
-    hard += (lo <= 1u || hi >= 254u) ? 1u : 0u;
-    nearc += (lo <= 8u || hi >= 247u) ? 1u : 0u;
-  }
-  for (int d = 32; d >= 1; d >>= 1) {
-    hard += __shfl_xor(hard, d);
-    nearc += __shfl_xor(nearc, d);
-  }
-  if (lane == 0) {
-    red[wave][0] = hard;
-    red[wave][1] = nearc;
-  }
-  __syncthreads();
-  if (tid < 2)
-    a.clip[2 * ((size_t)blockIdx.y * a.nclip + blockIdx.x) + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  wb_clip_count(static_cast<const T *>(a.in) + 2 * (size_t)blockIdx.y * a.wide_stride, (long)a.n * a.D,
+                a.clip + 2 * ((size_t)blockIdx.y * a.nclip + blockIdx.x));
 }
 
-// k_wb_level; the channel's capture selects the clip partials and the
-// parameter set.  The sum's order is k_wb_level's, a function of n alone.
+// the channel's capture selects the clip partials and the parameter set
 template <int W> __global__ __launch_bounds__(256) void k_wbb_level(WbbLevelArgs a) {
-  __shared__ double red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = (int)blockIdx.x; // the grid is C workgroups
-  const float *row = a.rows + (size_t)c * 2 * (size_t)a.stride;
-  const int np = (a.n + 1) >> 1; // pairs, the last one half empty at an odd n
-  double acc = 0.0;
-#pragma unroll 4
-  for (int p = tid; p < np; p += 256) {
-    const float *s = row + 4 * (size_t)p;
-    const bool two = 2 * p + 1 < a.n; // nothing past sample n - 1 is read
-    float r0, i0, r1 = 0.0f, i1 = 0.0f;
-    if (W == 16 && two) {
-      const float4 v = *reinterpret_cast<const float4 *>(s);
-      r0 = v.x;
-      i0 = v.y;
-      r1 = v.z;
-      i1 = v.w;
-    } else if (W >= 8) {
-      const float2 u = *reinterpret_cast<const float2 *>(s);
-      r0 = u.x;
-      i0 = u.y;
-      if (two) {
-        const float2 v = *reinterpret_cast<const float2 *>(s + 2);
-        r1 = v.x;
-        i1 = v.y;
-      }
-    } else {
-      r0 = s[0];
-      i0 = s[1];
-      if (two) {
-        r1 = s[2];
-        i1 = s[3];
-      }
-    }
-    acc += (double)r0 * (double)r0 + (double)i0 * (double)i0;
-    if (two) acc += (double)r1 * (double)r1 + (double)i1 * (double)i1;
-  }
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (tid != 0) return;
-  const double sum = ((red[0] + red[1]) + red[2]) + red[3];
+  const double sum = wb_row_power<W>(a.rows + (size_t)c * 2 * (size_t)a.stride, a.n);
+  if (threadIdx.x != 0) return;
   const int cap = a.chan_cap[c];
-  const uint32_t *clip = a.clip + 2 * (size_t)cap * a.nclip;
-  unsigned long long hard = 0, nearc = 0;
-  for (int k = 0; k < a.nclip; ++k) {
-    hard += clip[2 * k];
-    nearc += clip[2 * k + 1];
-  }
-  const double nn = (double)((long)a.n * a.D);
-  const double pw = sum / (double)a.n;
-  const double *sp = a.sp + 4 * (size_t)cap; // gain*factor, bias, floor, ceil
-  // the record as k_wb_level forms it
-  fmx_signal_level r;
-  const double rms = sqrt(fmax(1e-15, 0.5 * pw));
-  r.dbfs = 20.0 * log10(rms + 1e-12);
-  r.compensated_dbfs = r.dbfs - sp[0] + sp[1];
-  const double safeCeil = fmax(sp[3], sp[2] + 1.0);
-  const double norm = (r.compensated_dbfs - sp[2]) / (safeCeil - sp[2]);
-  const float l = (float)(norm * 120.0);
-  r.level120 = l < 0.0f ? 0.0f : (l > 120.0f ? 120.0f : l);
-  r.hard_clip_ratio = (double)hard / nn;
-  r.near_clip_ratio = (double)nearc / nn;
-  float *sm = a.sm + 2 * (size_t)c;
-  if (sm[1] == 0.0f) {
-    sm[0] = r.level120;
-    sm[1] = 1.0f;
-  } else {
-    const float alpha = (r.level120 > sm[0]) ? 0.42f : 0.18f;
-    sm[0] += (r.level120 - sm[0]) * alpha;
-  }
-  r.level120_smoothed = sm[0];
-  a.level[c] = r;
+  a.level[c] = wb_level_record(sum, 1.0, (double)a.n, a.clip + 2 * (size_t)cap * a.nclip, a.nclip,
+                               (double)((long)a.n * a.D), a.sp + 4 * (size_t)cap, a.sm + 2 * (size_t)c);
 }
 
 int launch_wbb_level(const WbbLevelArgs &a0, void *stream) {

@@ -2431,6 +2431,14 @@ struct WbBank {
   bool sig_pending = false;
   uint32_t *d_clip = nullptr; // [S][clip workgroups of a full block][2] (allocated on first use)
   float *d_sm = nullptr;      // [C][2] level smoothers
+  // fmx_wb_bank_set_iq_correction: Iqc's buffers with a
+  // capture dimension -- d_blk [S], d_partial [S][workgroups of a full
+  // block][5], d_tsum and tsum [C][2] -- allocated by the first set that
+  // leaves OFF.  iqc.mode and iqc.alpha are not used: every capture has its own
+  Iqc iqc;
+  WbbIqcMode *d_iq_mode = nullptr; // [S] mode and alpha, written with the blocks by k_bank_iqc_set on sA
+  std::vector<int> iq_mode;        // [S] the modes as of the calls queued so far: which kernels a call launches
+  int iq_on = 0, iq_auto = 0;      // captures out of OFF, captures in AUTO
 };
 WbBank *WBK(void *p) { return static_cast<WbBank *>(p); }
 void wbb_free(WbBank *b) {
@@ -2447,6 +2455,8 @@ void wbb_free(WbBank *b) {
   if (b->d_rows) hipFree(b->d_rows);
   if (b->d_clip) hipFree(b->d_clip);
   if (b->d_sm) hipFree(b->d_sm);
+  if (b->d_iq_mode) hipFree(b->d_iq_mode);
+  iqc_free(b->iqc);
   delete b;
 }
 
@@ -2476,8 +2486,15 @@ int wbb_run(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float 
   a.scale = static_cast<float>(std::ldexp(a.s16 ? 1.0 / 32768.0 : 1.0 / 255.0, -p.sexp));
   a.out = d_out;
   a.out_stride = out_stride;
-  int rc;
-  if ((rc = launch_wbb(a, h->sA)) != FMX_OK) {
+  int rc = FMX_OK;
+  if (b->iq_on == 0) {
+    rc = launch_wbb(a, h->sA);
+  } else { // estimator, finisher, corrected channelizer: one launch each for every capture
+    const WbbIqcArgs q{b->iqc.d_blk, b->d_iq_mode, b->iqc.d_partial, b->iqc.d_tsum};
+    if (b->iq_auto > 0) rc = launch_wbb_iqc_estimate(a, q, h->sA);
+    if (rc == FMX_OK) rc = launch_wbb_iqc(a, q, h->sA);
+  }
+  if (rc != FMX_OK) {
     h->err = std::string(who) + ": kernel launch failed";
     return rc;
   }
@@ -2547,6 +2564,9 @@ int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, c
       fpos[c] = wb_freq_mod(p, freq_hz[c]);
       chan_cap[c] = s;
     }
+  b->iqc.tsum.assign(2 * cn1, 0.0f);
+  for (int c = 0; c < Cn; ++c) wb_tap_sums(p, rows.data() + row * c, b->iqc.tsum.data() + 2 * c);
+  b->iq_mode.assign(n_captures, FMX_IQC_OFF);
   std::vector<WbbState> state(n_captures); // counter 0, nothing valid
   std::vector<double> sp(static_cast<size_t>(4) * n_captures);
   for (int s = 0; s < n_captures; ++s) {
@@ -2568,7 +2588,9 @@ int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, c
     wbb_free(b);
     return FMX_E_NOMEM;
   }
-  e = hipHostMalloc(reinterpret_cast<void **>(&b->stage), row * sizeof(uint16_t) + sizeof(uint32_t), hipHostMallocDefault);
+  // one channel's rows, its f mod Fs and its two tap sums
+  e = hipHostMalloc(reinterpret_cast<void **>(&b->stage), row * sizeof(uint16_t) + sizeof(uint32_t) + 2 * sizeof(float),
+                    hipHostMallocDefault);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev, hipEventDisableTiming);
   // synchronous copies: the tables are complete before the first call is queued
   if (e == hipSuccess) e = hipMemcpy(b->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
@@ -2613,6 +2635,14 @@ int fmx_wb_bank_set_freq(void *bank, int channel, int freq_hz) {
   // on the stage stream: after the calls queued so far, before later ones
   HIP_TRY(hipMemcpyAsync(b->d_w + row * channel, b->stage, row * sizeof(uint16_t), hipMemcpyHostToDevice, h->sA));
   HIP_TRY(hipMemcpyAsync(b->d_fpos + channel, b->stage + row, sizeof(uint32_t), hipMemcpyHostToDevice, h->sA));
+  // the channel's tap sums follow its rows (behind f mod Fs in the staging image)
+  float *ts = b->iqc.tsum.data() + 2 * static_cast<size_t>(channel);
+  wb_tap_sums(b->p, b->stage, ts);
+  if (b->iqc.d_tsum) {
+    std::memcpy(b->stage + row + 2, ts, 2 * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(b->iqc.d_tsum + 2 * static_cast<size_t>(channel), b->stage + row + 2, 2 * sizeof(float),
+                           hipMemcpyHostToDevice, h->sA));
+  }
   HIP_TRY(hipEventRecord(b->ev, h->sA));
   b->ev_set = true;
   return FMX_OK;
@@ -2964,19 +2994,35 @@ int fmx_wb_scan_process(void *scan, const void *d_wide, int n_out, fmx_signal_le
 
 /* ---- DC offset and IQ imbalance (fmx.h; kernels in fmx_wb_iqc.inc) ---- */
 namespace {
+// what fmx_wb_set_iq_correction and its siblings refuse (NULL: nothing)
+const char *iqc_refused(int mode, const fmx_iq_correction *fixed, double alpha) {
+  if (mode != FMX_IQC_OFF && mode != FMX_IQC_FIXED && mode != FMX_IQC_AUTO) return "unknown mode";
+  if (mode == FMX_IQC_FIXED && !fixed) return "FMX_IQC_FIXED needs the parameters";
+  if (mode == FMX_IQC_FIXED && !(std::isfinite(fixed->dc_i) && std::isfinite(fixed->dc_q) && std::isfinite(fixed->gain) &&
+                                 std::isfinite(fixed->cross)))
+    return "a parameter is not finite";
+  if (mode == FMX_IQC_FIXED && !(fixed->gain > 0.0)) return "gain must be positive";
+  if (mode == FMX_IQC_AUTO && !(alpha >= 0.0 && alpha <= 1.0)) return "alpha must lie in (0, 1] (0: 1 / 16)";
+  return nullptr;
+}
+// the block a set writes: FIXED's parameters; else the identity (AUTO: until
+// the first call's estimate); init = 0 restarts the smoothing
+FmxIqcBlock iqc_block(int mode, const fmx_iq_correction *fixed, int s16) {
+  FmxIqcBlock v{};
+  v.x = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
+  if (mode == FMX_IQC_FIXED) v.x = *fixed;
+  const double unit = s16 ? 32768.0 : 255.0;
+  v.k[0] = static_cast<float>(v.x.dc_i * unit);
+  v.k[1] = static_cast<float>(v.x.dc_q * unit);
+  v.k[2] = static_cast<float>(v.x.gain);
+  v.k[3] = static_cast<float>(v.x.cross);
+  return v;
+}
 // The mode of one object's Iqc: validates, allocates on the first mode other
 // than OFF, and queues the block's rewrite on sA (behind the calls queued so
 // far, ahead of later ones).
 int iqc_set(Handle *h, Iqc &q, const WbPlan &p, const char *who, int mode, const fmx_iq_correction *fixed, double alpha) {
-  const char *bad = nullptr;
-  if (mode != FMX_IQC_OFF && mode != FMX_IQC_FIXED && mode != FMX_IQC_AUTO) bad = "unknown mode";
-  else if (mode == FMX_IQC_FIXED && !fixed) bad = "FMX_IQC_FIXED needs the parameters";
-  else if (mode == FMX_IQC_FIXED && !(std::isfinite(fixed->dc_i) && std::isfinite(fixed->dc_q) &&
-                                      std::isfinite(fixed->gain) && std::isfinite(fixed->cross)))
-    bad = "a parameter is not finite";
-  else if (mode == FMX_IQC_FIXED && !(fixed->gain > 0.0)) bad = "gain must be positive";
-  else if (mode == FMX_IQC_AUTO && !(alpha >= 0.0 && alpha <= 1.0)) bad = "alpha must lie in (0, 1] (0: 1 / 16)";
-  if (bad) {
+  if (const char *bad = iqc_refused(mode, fixed, alpha)) {
     h->err = std::string(who) + ": " + bad;
     return FMX_E_INVALID;
   }
@@ -3001,16 +3047,8 @@ int iqc_set(Handle *h, Iqc &q, const WbPlan &p, const char *who, int mode, const
       return FMX_E_NOMEM;
     }
   }
-  FmxIqcBlock v{}; // AUTO: identity until the first call's estimate; init = 0 restarts the smoothing
-  v.x = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
-  if (mode == FMX_IQC_FIXED) v.x = *fixed;
-  const double unit = s16 ? 32768.0 : 255.0;
-  v.k[0] = static_cast<float>(v.x.dc_i * unit);
-  v.k[1] = static_cast<float>(v.x.dc_q * unit);
-  v.k[2] = static_cast<float>(v.x.gain);
-  v.k[3] = static_cast<float>(v.x.cross);
   int rc;
-  if ((rc = launch_iqc_set(q.d_blk, v, h->sA)) != FMX_OK) {
+  if ((rc = launch_iqc_set(q.d_blk, iqc_block(mode, fixed, s16), h->sA)) != FMX_OK) {
     h->err = std::string(who) + ": kernel launch failed";
     return rc;
   }
@@ -3039,7 +3077,7 @@ Wb *iqc_wb(void *wb, const char *who) {
   Wb *w = W(wb);
   if (!w) return nullptr;
   const char *bad = nullptr;
-  if (w->kind == WB_KIND_BANK) bad = "the capture bank has no IQ correction (out of scope)";
+  if (w->kind == WB_KIND_BANK) bad = "a capture bank takes fmx_wb_bank_set_iq_correction / fmx_wb_bank_iq_correction";
   else if (w->kind != WB_KIND_WB) bad = "not an fmx_wb object";
   else if (w->rational) bad = "an object of fmx_wb_create_rational at Q > 1 has no IQ correction (out of scope)";
   if (bad) {
@@ -3052,7 +3090,7 @@ WbScan *iqc_scan(void *scan, const char *who) {
   WbScan *s = WS(scan);
   if (!s) return nullptr;
   if (s->kind != WB_KIND_SCAN) {
-    s->h->err = std::string(who) + (s->kind == WB_KIND_BANK ? ": the capture bank has no IQ correction (out of scope)"
+    s->h->err = std::string(who) + (s->kind == WB_KIND_BANK ? ": a capture bank takes fmx_wb_bank_set_iq_correction / fmx_wb_bank_iq_correction"
                                                             : ": not an fmx_wb_scan object");
     return nullptr;
   }
@@ -3079,6 +3117,95 @@ int fmx_wb_scan_iq_correction(void *scan, fmx_iq_correction *h_out) {
   WbScan *s = iqc_scan(scan, "fmx_wb_scan_iq_correction");
   if (!s) return FMX_E_INVALID;
   return iqc_get(s->h, s->iqc, "fmx_wb_scan_iq_correction", h_out);
+}
+
+
+/* ---- the bank's correction, per capture (fmx.h; kernels in fmx_wb_bank_iqc.inc) ---- */
+namespace {
+WbBank *iqc_bank(void *bank, const char *who) {
+  WbBank *b = WBK(bank);
+  if (!b) return nullptr;
+  if (b->kind != WB_KIND_BANK) {
+    b->h->err = std::string(who) + ": not a capture bank";
+    return nullptr;
+  }
+  return b;
+}
+} // namespace
+
+int fmx_wb_bank_set_iq_correction(void *bank, int capture, int mode, const fmx_iq_correction *fixed, double alpha) {
+  const char *who = "fmx_wb_bank_set_iq_correction";
+  WbBank *b = iqc_bank(bank, who);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  const char *bad = capture < -1 || capture >= b->S ? "capture out of range" : iqc_refused(mode, fixed, alpha);
+  if (bad) {
+    h->err = std::string(who) + ": " + bad;
+    return FMX_E_INVALID;
+  }
+  Iqc &q = b->iqc;
+  if (!q.d_blk && mode == FMX_IQC_OFF) return FMX_OK; // every capture is in OFF, and nothing exists yet
+  const WbPlan &p = b->p;
+  const int s16 = p.format == FMX_WB_S16;
+  HIP_TRY(hipSetDevice(h->device));
+  if (!q.d_blk) {
+    const size_t nS = static_cast<size_t>(b->S);
+    const size_t n_partial = nS * static_cast<size_t>(iqc_workgroups(static_cast<long>(p.block) * p.D, s16)) * 5;
+    std::vector<FmxIqcBlock> blk(nS, iqc_block(FMX_IQC_OFF, nullptr, s16));
+    std::vector<WbbIqcMode> tab(nS, WbbIqcMode{1.0 / 16.0, FMX_IQC_OFF, 0});
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&q.d_blk), nS * sizeof(FmxIqcBlock));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_iq_mode), nS * sizeof(WbbIqcMode));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&q.d_partial), n_partial * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&q.d_tsum), q.tsum.size() * sizeof(float));
+    // synchronous: the tables are complete before a corrected call is queued
+    // (k_bank_iqc_set and fmx_wb_bank_set_freq keep them current from here on)
+    if (e == hipSuccess) e = hipMemcpy(q.d_blk, blk.data(), nS * sizeof(FmxIqcBlock), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b->d_iq_mode, tab.data(), nS * sizeof(WbbIqcMode), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(q.d_tsum, q.tsum.data(), q.tsum.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      iqc_free(q);
+      if (b->d_iq_mode) hipFree(b->d_iq_mode);
+      b->d_iq_mode = nullptr;
+      h->err = std::string(who) + ": " + hipGetErrorString(e);
+      return FMX_E_NOMEM;
+    }
+  }
+  // a one-thread kernel on sA: behind the calls queued so far, ahead of later ones
+  const WbbIqcArgs qa{q.d_blk, b->d_iq_mode, q.d_partial, q.d_tsum};
+  int rc;
+  if ((rc = launch_wbb_iqc_set(qa, b->S, capture, iqc_block(mode, fixed, s16), mode, alpha == 0.0 ? 1.0 / 16.0 : alpha,
+                               h->sA)) != FMX_OK) {
+    h->err = std::string(who) + ": kernel launch failed";
+    return rc;
+  }
+  for (int s = capture < 0 ? 0 : capture; s < (capture < 0 ? b->S : capture + 1); ++s) b->iq_mode[s] = mode;
+  b->iq_on = b->iq_auto = 0;
+  for (int m : b->iq_mode) {
+    b->iq_on += m != FMX_IQC_OFF;
+    b->iq_auto += m == FMX_IQC_AUTO;
+  }
+  return FMX_OK;
+}
+
+int fmx_wb_bank_iq_correction(void *bank, int capture, fmx_iq_correction *h_out) {
+  const char *who = "fmx_wb_bank_iq_correction";
+  WbBank *b = iqc_bank(bank, who);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (capture < 0 || capture >= b->S || !h_out) {
+    h->err = std::string(who) + (h_out ? ": capture out of range (one capture per call)" : ": null h_out");
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->sA));
+  if (b->iq_mode[capture] == FMX_IQC_OFF) {
+    *h_out = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
+    return FMX_OK;
+  }
+  FmxIqcBlock v;
+  HIP_TRY(hipMemcpy(&v, b->iqc.d_blk + capture, sizeof(v), hipMemcpyDeviceToHost));
+  *h_out = v.x;
+  return FMX_OK;
 }
 
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes) {

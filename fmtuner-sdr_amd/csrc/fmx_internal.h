@@ -485,6 +485,27 @@ struct WbbLevelArgs {
 };
 int launch_wbb_level(const WbbLevelArgs &a, void *stream);
 
+// ---- the bank's DC / IQ-imbalance correction (fmx_wb_bank_iqc.inc) ----
+// one capture's mode and smoothing, kept on the device beside its FmxIqcBlock:
+// k_bank_iqc_set writes it, the estimator, the finisher and k_bank_iqc read it
+struct WbbIqcMode {
+  double alpha; // AUTO's smoothing, in (0, 1]
+  int mode;     // FMX_IQC_*
+  int pad;
+};
+struct WbbIqcArgs {
+  FmxIqcBlock *blk;    // [S]
+  WbbIqcMode *mode;    // [S]
+  long long *partial;  // [S][workgroups of the call][5] the estimator's sums
+  const float *tsum;   // [C][2] tap sums (SR, SI)
+};
+// capture's block, mode and alpha (-1: every capture's) on the stream
+int launch_wbb_iqc_set(const WbbIqcArgs &q, int S, int capture, const FmxIqcBlock &v, int mode, double alpha, void *stream);
+// the estimator and the finisher over row s of the call's input for every capture in AUTO
+int launch_wbb_iqc_estimate(const WbbArgs &a, const WbbIqcArgs &q, void *stream);
+// launch_wbb with k_bank_iqc in k_wbb's place
+int launch_wbb_iqc(const WbbArgs &a, const WbbIqcArgs &q, void *stream);
+
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps
 

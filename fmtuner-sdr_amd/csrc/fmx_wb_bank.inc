@@ -98,7 +98,10 @@ __global__ void k_wbb_set_params(double *sp, int S, int capture, double v0, doub
   }
 }
 
-int launch_wbb(const WbbArgs &a0, void *stream) {
+// A bank call around `launch`, which starts the channelizer kernel (k_wbb, or
+// k_bank_iqc of fmx_wb_bank_iqc.inc): the checks and the tiling ahead of it,
+// k_wbb_hist behind it.
+template <class Launch> static int wbb_run(const WbbArgs &a0, void *stream, Launch launch) {
   WbbArgs a = a0;
   if (a.S <= 0 || a.n_out <= 0) return FMX_OK;
   if (a.S > FMX_WBB_CAPTURES_MAX || a.G < 0 || a.G > FMX_WBB_GROUPS_MAX || a.C < 0 ||
@@ -113,13 +116,19 @@ int launch_wbb(const WbbArgs &a0, void *stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.G > 0) {
     const dim3 grid((unsigned)((a.n_out + 16 * a.nt - 1) / (16 * a.nt)), (unsigned)a.G);
-    const int rc = WB_LAUNCH(k_wbb, a.s16, (a.D & 1) == 0, grid, smem, st, a);
+    const int rc = launch(a, smem, grid, st);
     if (rc != FMX_OK) return rc;
   }
   const dim3 hgrid((unsigned)((a.L - 1 + 255) / 256), (unsigned)a.S);
   if (a.s16) hipLaunchKernelGGL(k_wbb_hist<int16_t>, hgrid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_wbb_hist<uint8_t>, hgrid, dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
+}
+
+int launch_wbb(const WbbArgs &a0, void *stream) {
+  return wbb_run(a0, stream, [](const WbbArgs &a, size_t smem, dim3 grid, hipStream_t st) {
+    return WB_LAUNCH(k_wbb, a.s16, (a.D & 1) == 0, grid, smem, st, a);
+  });
 }
 
 int launch_wbb_set_state(WbbState *state, int S, int capture, uint64_t counter, void *stream) {

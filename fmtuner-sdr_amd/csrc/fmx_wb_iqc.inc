@@ -34,10 +34,11 @@ static __device__ __forceinline__ void iqc_acc(long long s[5], int vi, int vq) {
   s[4] += (long long)vi * vq;
 }
 
-// T = uint8_t: v = 2 b - 255; T = int16_t: v.  Workgroup w sums the samples
-// [w SPW, (w + 1) SPW): by 16-B loads when the input is 16-B aligned (al16),
-// sample by sample otherwise.  partial[w][5].
-template <typename T> __global__ __launch_bounds__(256) void k_iqc_sums(const void *in, long n_in, int al16, long long *partial) {
+// T = uint8_t: v = 2 b - 255; T = int16_t: v.  Workgroup blockIdx.x sums the
+// samples [w SPW, (w + 1) SPW) of the n_in at `in`: by 16-B loads when the
+// input is 16-B aligned (al16), sample by sample otherwise.  dst[5].
+// (k_iqc_sums; k_bank_iqc_sums of fmx_wb_bank_iqc.inc on a capture's row)
+template <typename T> static __device__ __forceinline__ void iqc_sum_workgroup(const void *in, long n_in, int al16, long long *dst) {
   constexpr int SPV = 16 / (2 * (int)sizeof(T));        // samples per 16-B load
   constexpr long SPW = IQC_WG_BYTES / (2 * sizeof(T)); // samples per workgroup
   __shared__ long long red[4][5];
@@ -74,12 +75,17 @@ template <typename T> __global__ __launch_bounds__(256) void k_iqc_sums(const vo
     if (lane == 0) red[wave][j] = s[j];
   }
   __syncthreads();
-  if (tid < 5) partial[5 * (size_t)blockIdx.x + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  if (tid < 5) dst[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
-__global__ __launch_bounds__(64) void k_iqc_finish(const long long *partial, int nwg, long n_in, double alpha, double unit,
-                                                   FmxIqcBlock *blk) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// partial[w][5]
+template <typename T> __global__ __launch_bounds__(256) void k_iqc_sums(const void *in, long n_in, int al16, long long *partial) {
+  iqc_sum_workgroup<T>(in, n_in, al16, partial + 5 * (size_t)blockIdx.x);
+}
+
+// one thread: the nwg partials in index order, then fmx_iqc_finish on the block
+static __device__ __forceinline__ void iqc_finish_block(const long long *partial, int nwg, long n_in, double alpha,
+                                                        double unit, FmxIqcBlock *blk) {
   long long s[5] = {0, 0, 0, 0, 0};
   for (int w = 0; w < nwg; ++w)
 #pragma unroll
@@ -87,6 +93,12 @@ __global__ __launch_bounds__(64) void k_iqc_finish(const long long *partial, int
   FmxIqcBlock b = *blk;
   fmx_iqc_finish(s, n_in, alpha, unit, &b);
   *blk = b;
+}
+
+__global__ __launch_bounds__(64) void k_iqc_finish(const long long *partial, int nwg, long n_in, double alpha, double unit,
+                                                   FmxIqcBlock *blk) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  iqc_finish_block(partial, nwg, n_in, alpha, unit, blk);
 }
 
 // FIXED (and the restart of AUTO, init = 0): the whole block

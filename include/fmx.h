@@ -47,7 +47,8 @@
 extern "C" {
 #endif
 
-/* ABI history: the DC / IQ-imbalance correction (fmx_wb_set_iq_correction, fmx_wb_iq_correction,
+/* ABI history: the bank's correction per capture (fmx_wb_bank_set_iq_correction, fmx_wb_bank_iq_correction) arrived at 13
+ * without a bump: additions only; the DC / IQ-imbalance correction (fmx_wb_set_iq_correction, fmx_wb_iq_correction,
  * fmx_wb_scan_set_iq_correction, fmx_wb_scan_iq_correction, fmx_iq_estimate, fmx_iq_correction, FMX_IQC_*)
  * arrived at 13 without a bump, as the bank and the rational rates did: additions only; rational wide rates (fmx_wb_create_rational, fmx_wb_ratio, fmx_wb_weights_rational,
  * fmx_wb_rational_geometry: 20, 10 and 2.048 MS/s captures channelized at P / Q) arrived at 13 without a bump,
@@ -520,8 +521,9 @@ int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int min_spacing, 
  * a bad mode, an alpha outside the range, a NULL `fixed` in FIXED, a
  * non-finite field or gain <= 0.  Out of scope, FMX_E_INVALID as well: an
  * object made by fmx_wb_create_rational at Q > 1 (19.2 and 24 MS/s are
- * integer rates) and the capture bank; frequency-dependent imbalance is not
- * modelled.  fmx_wb_iq_correction / fmx_wb_scan_iq_correction wait for the
+ * integer rates); frequency-dependent imbalance is not modelled.  A capture
+ * bank takes fmx_wb_bank_set_iq_correction below, and these four calls refuse
+ * it.  fmx_wb_iq_correction / fmx_wb_scan_iq_correction wait for the
  * queued calls and return the parameters as of the last one (identity in OFF).
  * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
 typedef struct { double dc_i, dc_q, gain, cross; } fmx_iq_correction; /* units of x */
@@ -535,6 +537,34 @@ int fmx_wb_scan_iq_correction(void *scan, fmx_iq_correction *h_out);
  * test can check against.  FMX_E_INVALID for n_samples <= 0, a NULL argument
  * or an unknown format. */
 int fmx_iq_estimate(const void *h_raw, int format, long n_samples, fmx_iq_correction *out);
+
+/* ---- capture bank: DC offset and IQ imbalance per capture ----
+ * Every front end behind a bank has its own DC and its own I/Q mismatch, so
+ * every capture has its own mode, parameters, alpha and smoothed moments.
+ * Capture s behaves as an fmx_wb object with the same configuration and
+ * frequencies, fed row s, that was given the same fmx_wb_set_iq_correction
+ * calls at the same points of its stream: its rows -- and through them
+ * fmx_wb_bank_process_block's outputs and fmx_wb_bank_signal's records -- and
+ * the read-back agree bit for bit in every mode, a capture left in OFF beside
+ * corrected ones included.  AUTO's sums run over the capture's own n * D raw
+ * samples of the call (the padding of a row is never read); the clip ratios
+ * stay those of the raw samples; an empty capture is legal in every mode, and
+ * in AUTO its read-back follows the estimator on its row.  The set is ordered
+ * on the stage stream, holds from the next process call on and restarts that
+ * capture's estimate; fmx_wb_bank_reset and fmx_wb_bank_set_freq leave the
+ * estimate alone.  A call costs one estimator, one finisher and one
+ * channelizer launch whatever the number of captures, with no host
+ * synchronisation; a bank whose captures are all in OFF launches what it
+ * launched before these calls existed.
+ * FMX_E_INVALID (message naming the function) for a capture outside
+ * [-1, n_captures), whatever fmx_wb_set_iq_correction refuses, a NULL h_out,
+ * capture -1 in the read-back and an object that is not a bank.
+ * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
+/* capture's correction (-1: every capture's); modes, parameters, alpha, validation,
+ * ordering and the estimator exactly as fmx_wb_set_iq_correction */
+int fmx_wb_bank_set_iq_correction(void *bank, int capture, int mode, const fmx_iq_correction *fixed, double alpha);
+/* waits for the queued calls; capture's parameters as of the last one (identity in OFF) */
+int fmx_wb_bank_iq_correction(void *bank, int capture, fmx_iq_correction *h_out);
 
 /* ---- device memory helpers (so C/FFI callers need no HIP headers) ---- */
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes);

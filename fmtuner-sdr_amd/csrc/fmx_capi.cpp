@@ -1259,20 +1259,26 @@ static int step_sC(Handle *h, const Step &s) {
     r.sched_stride = h->t_rds.stride;
     r.out = h->rds_in[s.buf];
     r.out_stride = h->rds_stride;
-    // <= FMX_RS_TMAX output tiles per workgroup (8 parts of 23 tiles at a
-    // 4096-sample block); from 256 channel groups (4096 channels) on, <= 46:
-    // about half as many workgroups beside the other streams' (round 6, with
-    // k_rs's schedule no longer staged in LDS): 4096 ch 0.5790 -> 0.5707 and
-    // 0.5804 -> 0.5718 ms in two 4-rep A/Bs; at 2048 ch the longer parts were
-    // slower, 0.3453 -> 0.3638 (profiles/r06k_ab_rs_parts_*.txt, r06m_*).
-    // Fewer channels, finer parts: with few channel groups k_rs is latency --
-    // one wave per part walking its tiles -- so below 2048 channels parts of
-    // <= 6 tiles (1024 ch 0.2809 -> 0.2444 ms, 256 ch 0.2465 -> 0.2033) and
-    // <= 12 at 2048 (0.3410 -> 0.3379, 0.3445 -> 0.3420 in r06c)
-    // (profiles/r06z4_*, r06z5_*)
+    // A workgroup takes FMX_RS_G = 4 adjacent channel groups and a run of
+    // output tiles, and builds each tile's band matrix once for its groups;
+    // a step is one (tile, group), tiles per workgroup = steps / G rounded up.
+    // Steps per workgroup by channel count, each set by interleaved A/B:
+    // from 256 channel groups (4096 channels) on <= 92 (23 tiles, 8 parts at
+    // a 4096-sample block, 512 workgroups): base 0.5149, 46 steps 0.5107,
+    // 69 steps 0.5041, 92 steps 0.5051 ms (6 x 100 steps; G = 2 0.5112 / 92
+    // steps 0.5161; G = 8 0.5188 / 0.5181 / 184 steps 0.5269 against 0.5216:
+    // profiles/r07_ab_rs_shared_tile_*.txt) -- fewer, longer workgroups beside
+    // the other streams', as round 6 found for one group per workgroup
+    // (r06k, r06m).  Fewer channels, finer parts: with few channel groups
+    // k_rs is latency -- one wave per part walking its steps -- so <= 12
+    // steps at 2048 channels (24 no better: 0.3093 against 0.3109, base
+    // 0.3095) and <= 6 below (1024 ch: base 0.2328, 6 steps 0.2218, 12 steps
+    // 0.2223), where round 6 had put the tiles (r06z4, r06z5).
     const int rs_groups = (h->C + 15) / 16;
     const int rs_tiles = (h->t_rds.stride + 15) / 16,
-              rs_tmax = rs_groups >= 256 ? 46 : (rs_groups >= 128 ? FMX_RS_TMAX : 6);
+              rs_steps = rs_groups >= 256 ? FMX_RS_BIG : (rs_groups >= 128 ? FMX_RS_TMAX : FMX_RS_SMALL),
+              rs_tmax = (rs_steps + FMX_RS_G - 1) / FMX_RS_G;
+    r.gpw = FMX_RS_G;
     r.parts = std::max(1, (rs_tiles + rs_tmax - 1) / rs_tmax);
     KBind t(h, FMX_K_RS, h->sC, nullptr);
     if (!FMX_SKIP(rds) && !FMX_SKIP(krs)) {

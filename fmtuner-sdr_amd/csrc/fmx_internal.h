@@ -195,7 +195,8 @@ struct RsArgs {
   int sched_stride;
   float *out;           // RDS-rate rows
   int out_stride;
-  int parts;            // workgroups per 16 channels (each a contiguous run of output tiles)
+  int parts;            // workgroups per gpw channel groups (each a contiguous run of output tiles)
+  int gpw;              // 16-channel groups per workgroup (even): a tile's band matrix is built once for them
 };
 
 // launchers (fmx_kernels.hip); stream is a hipStream_t
@@ -224,8 +225,20 @@ struct ResetArgs;
 int launch_rds_sym(const RdsArgs &a, void *stream);  // k_rds alone: the call's symbols
 int launch_ring_fill(const ResetArgs &a, void *stream); // every channel's RDS ring refilled where ring_ok = 0
 int launch_bits(const RdsArgs &a, void *stream);     // k_bits alone: the bit decoders
+// k_rs launch geometry (fmx_capi.cpp): FMX_RS_G 16-channel groups per
+// workgroup, and per workgroup at most this many steps -- a step is one
+// 16-output tile of one group -- by channel count
+#ifndef FMX_RS_G
+#define FMX_RS_G 4
+#endif
+#ifndef FMX_RS_BIG
+#define FMX_RS_BIG 92   // from 4096 channels on
+#endif
 #ifndef FMX_RS_TMAX
-#define FMX_RS_TMAX 12 // k_rs: output tiles (of 16) per workgroup at most from 2048 channels (46 from 4096 on, 6 below 2048: fmx_capi.cpp)
+#define FMX_RS_TMAX 12  // from 2048 channels
+#endif
+#ifndef FMX_RS_SMALL
+#define FMX_RS_SMALL 6  // below 2048 channels
 #endif
 int launch_rs(const RsArgs &a, void *stream);
 int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sample0, int n_samples,

@@ -1658,23 +1658,28 @@ __device__ __forceinline__ void rds_bits_store(FmxRdsState &g, const RdsBits &b)
 typedef float rs_f32x4 __attribute__((ext_vector_type(4)));
 // the first window sample of a tile (a multiple of 4) from its row-0 entry
 // (lane 0's; wave-uniform)
-__device__ __forceinline__ int rs_tile_k0(const FmxSched &e) {
-  const uint32_t p0 = __builtin_amdgcn_readlane(e.packed, 0);
+__device__ __forceinline__ int rs_k0_of(uint32_t p0) {
   const int i0 = p0 & 0xFFFF;
   return ((((p0 >> 24) & 1) ? i0 - 1 : i0) - (FMX_RDS_RS_SUB - 1)) & ~3;
+}
+__device__ __forceinline__ int rs_tile_k0(const FmxSched &e) {
+  return rs_k0_of(__builtin_amdgcn_readlane(e.packed, 0));
 }
 // 16 samples of a channel (quarter lq of the tile's 64) as four 16-B loads
 // (4-sample groups lie wholly in the history, the block or past it: k0 and n
 // are multiples of 4); unconditional loads (a branch here would make the
 // compiler wait for them at the join): samples past the block or a lane
-// without a channel read mrow[0] and are zeroed when written to LDS
+// without a channel read mrow[0] and are zeroed when written to LDS.  The
+// address is a base and an offset each picked by a select (the nested pointer
+// conditional compiled to two exec-mask branches per load)
 __device__ __forceinline__ void rs_load_w(const float *mrow, const float *wrow, bool lcv, int n, int lq, int k0,
                                           float4 (&v)[4]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int k = k0 + 16 * lq + 4 * j;
-    const float *p = (!lcv || k >= n) ? mrow : (k < 0 ? wrow + k : mrow + k);
-    v[j] = *reinterpret_cast<const float4 *>(p);
+    const bool ok = k < (lcv ? n : INT_MIN);
+    const float *base = (ok && k < 0) ? wrow : mrow;
+    v[j] = *reinterpret_cast<const float4 *>(base + (ok ? k : 0));
   }
 }
 // ... written to the channel's window row, transposed (samples 16 lq + 4 j + e:
@@ -1683,7 +1688,7 @@ __device__ __forceinline__ void rs_store_w(float *xrow, bool lcv, int n, int lq,
   float4 w[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const bool ok = lcv && k0 + 16 * lq + 4 * j < n;
+    const bool ok = k0 + 16 * lq + 4 * j < (lcv ? n : INT_MIN);
     w[j] = ok ? v[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
   *reinterpret_cast<float4 *>(&xrow[4 * lq]) = make_float4(w[0].x, w[1].x, w[2].x, w[3].x);
@@ -1693,9 +1698,12 @@ __device__ __forceinline__ void rs_store_w(float *xrow, bool lcv, int n, int lq,
 }
 // one tile: 16 outputs (rows, lane & 15 = r, entry en of row r) x 16
 // channel columns (B: the window row xrow of column r), K = the window in
-// steps of 4 (lane >> 4 = kk); D: lane (column r, outputs 4 kk .. 4 kk + 3)
-__device__ __forceinline__ rs_f32x4 rs_tile(const float (*tab)[FMX_RDS_RS_SUB + 1], const float *xrow,
-                                           const FmxSched &en, int kk) {
+// steps of 4 (lane >> 4 = kk); D: lane (column r, outputs 4 kk .. 4 kk + 3).
+// In two parts: rs_tile_build makes A (hv, this lane's 16 K steps of row r)
+// and the tile's K-step count from the schedule alone -- the same for every
+// channel -- and rs_tile_mma multiplies it with one 16-channel group's window
+__device__ __forceinline__ int rs_tile_build(const float (*tab)[FMX_RDS_RS_SUB + 1], const FmxSched &en, int kk,
+                                             float (&hv)[RS_KS]) {
   const int i = en.packed & 0xFFFF, b = (en.packed >> 16) & 0xFF;
   const bool bnd = (en.packed >> 24) & 1;
   const int s_r = (bnd ? i - 1 : i) - (FMX_RDS_RS_SUB - 1); // the window's oldest sample
@@ -1714,7 +1722,17 @@ __device__ __forceinline__ rs_f32x4 rs_tile(const float (*tab)[FMX_RDS_RS_SUB + 
   // (1 - mu) h_b + mu h_b+1, one MFMA chain (the reference interpolates the
   // two dot products, (1 - mu) y0 + mu y1: the same sum in another order)
   const float mu = en.mu, mu1 = 1.0f - mu;
-  float hv[RS_KS], xv[RS_KS];
+#pragma unroll
+  for (int st = 0; st < RS_KS; ++st) {
+    const int m = m0 + 4 * st;
+    const int mc = min(max(m, 0), FMX_RDS_RS_SUB);
+    const bool in = m >= 0 && m <= FMX_RDS_RS_SUB;
+    hv[st] = in ? mu1 * tab[row0][mc] + mu * tab[row1][mc] : 0.0f;
+  }
+  return ks;
+}
+__device__ __forceinline__ rs_f32x4 rs_tile_mma(const float *xrow, const float (&hv)[RS_KS], int ks, int kk) {
+  float xv[RS_KS];
 #pragma unroll
   for (int q = 0; q < RS_KS / 4; ++q) { // samples 4 st + kk, st = 4 q .. 4 q + 3
     const float4 x4 = *reinterpret_cast<const float4 *>(&xrow[RS_XS * kk + 4 * q]);
@@ -1723,14 +1741,11 @@ __device__ __forceinline__ rs_f32x4 rs_tile(const float (*tab)[FMX_RDS_RS_SUB + 
     xv[4 * q + 2] = x4.z;
     xv[4 * q + 3] = x4.w;
   }
-#pragma unroll
-  for (int st = 0; st < RS_KS; ++st) {
-    const int m = m0 + 4 * st;
-    const int mc = min(max(m, 0), FMX_RDS_RS_SUB);
-    const bool in = m >= 0 && m <= FMX_RDS_RS_SUB;
-    hv[st] = in ? mu1 * tab[row0][mc] + mu * tab[row1][mc] : 0.0f;
-  }
   rs_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  // ks is the same for a tile's every group: kept an opaque scalar here, so
+  // that each cut below stays a scalar compare (hoisted out of the group loop
+  // the 16 conditions are 16 lane masks: 32 SGPRs, and spills)
+  asm volatile("" : "+s"(ks));
 #pragma unroll
   for (int st = 0; st < RS_KS; ++st)
     if (st < ks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[st], xv[st], acc, 0, 0, 0);
@@ -1738,14 +1753,27 @@ __device__ __forceinline__ rs_f32x4 rs_tile(const float (*tab)[FMX_RDS_RS_SUB + 
 }
 // the resampler's tap rows: row b < 32 branch b on the window, row 32
 // branch 0 on the window shifted by one (the boundary pair's second branch)
-__device__ __forceinline__ void rs_fill_tab(float (*tab)[FMX_RDS_RS_SUB + 1], const FmxDesign *D, int lane, int nl) {
-  for (int idx = lane; idx < (FMX_NPFB + 1) * (FMX_RDS_RS_SUB + 1); idx += nl) {
+// (one wave: every lane's loads are issued before the first is written to
+// LDS -- as a loop the fill waited for each load in turn, 14 L2 round trips
+// at the start of every workgroup)
+__device__ __forceinline__ void rs_fill_tab(float (*tab)[FMX_RDS_RS_SUB + 1], const FmxDesign *D, int lane) {
+  constexpr int NT = (FMX_NPFB + 1) * (FMX_RDS_RS_SUB + 1), NI = (NT + 63) / 64;
+  const float *hs = D->rds_rs_h; // [branch][26]
+  float h[NI];
+#pragma unroll
+  for (int it = 0; it < NI; ++it) {
+    const int idx = min(lane + 64 * it, NT - 1);
     const int b = idx / (FMX_RDS_RS_SUB + 1), m = idx % (FMX_RDS_RS_SUB + 1);
-    const float *hs = D->rds_rs_h; // [branch][26]
-    float h;
-    if (b < FMX_NPFB) h = m < FMX_RDS_RS_SUB ? hs[b * FMX_RDS_RS_SUB + FMX_RDS_RS_SUB - 1 - m] : 0.0f;
-    else h = m >= 1 ? hs[FMX_RDS_RS_SUB - m] : 0.0f;
-    tab[b][m] = h;
+    // the tap this entry holds, or (a row's leading / trailing zero) any valid one, dropped below
+    const bool tap = b < FMX_NPFB ? m < FMX_RDS_RS_SUB : m >= 1;
+    const int src = b < FMX_NPFB ? b * FMX_RDS_RS_SUB + FMX_RDS_RS_SUB - 1 - m : FMX_RDS_RS_SUB - m;
+    const float t = hs[tap ? src : 0];
+    h[it] = tap ? t : 0.0f;
+  }
+#pragma unroll
+  for (int it = 0; it < NI; ++it) {
+    const int idx = lane + 64 * it;
+    if (idx < NT) tab[idx / (FMX_RDS_RS_SUB + 1)][idx % (FMX_RDS_RS_SUB + 1)] = h[it];
   }
 }
 
@@ -3719,11 +3747,18 @@ int launch_pilot(const PilotArgs &a0, void *stream) {
  * 4 columns per K step, with the MPX of 16 channels (B = 4 samples x 16
  * channels).  FP32 products, sums in blocks of 4 (the reference sums
  * sequentially; k_fe8's FMA chains it replaces differed the same way, by a
- * few ulp).  One wave per workgroup; workgroup (x, y) takes channels
- * 16 x .. 16 x + 15 and the y-th contiguous run of 16-output tiles.  With it,
- * k_fe8 leaves out the resampler: a front end without it ran 0.777 against
- * 0.847 ms per pipelined step (profiles/r03h_ab_lds_history_nors.txt). */
-#define RS_TMAX FMX_RS_TMAX // output tiles per workgroup at most (fmx_capi.cpp sizes parts)
+ * few ulp).  One wave per workgroup; workgroup (x, y) takes the G = a.gpw
+ * adjacent 16-channel groups from channel 16 G x on and the y-th contiguous
+ * run of 16-output tiles (fmx_capi.cpp sizes G and the runs).  A depends on
+ * the schedule alone, so the workgroup builds it once per tile and multiplies
+ * it with each of its groups' windows in turn; the window loads run two
+ * (tile, group) steps ahead with nothing conditional between them, so that a
+ * step waits for the older loads only -- that, and a table fill whose loads
+ * go out together, is where the time went: the build shared alone moved
+ * nothing (profiles/r07_ab_rs_shared_tile_*.txt).
+ * With k_rs, k_fe8 leaves out the resampler: a front end without it ran
+ * 0.777 against 0.847 ms per pipelined step
+ * (profiles/r03h_ab_lds_history_nors.txt). */
 // <= 96 VGPRs (five waves per SIMD): a k_rs wave beside two k_fe8 waves (168
 // each) and a k_pll wave (80)
 struct RsLds {
@@ -3741,9 +3776,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_
   auto &tab = RL.tab;
   auto &xs = RL.xs;
   const int lane = threadIdx.x;
-  const int c0 = blockIdx.x * 16;
+  const int G = a.gpw;
+  const int c0 = blockIdx.x * G * 16;
+  // this workgroup's channel groups that start below C (>= 1 by the grid)
+  const int gv = min(G, (a.C - c0 + 15) / 16);
   const FmxDesign *__restrict__ D = a.des;
-  rs_fill_tab(tab, D, lane, 64);
+  rs_fill_tab(tab, D, lane);
   // one schedule for every channel (the RDS timing set is never reset per
   // channel: SubcarrierSet::reset leaves the resampler alone,
   // subcarrier.cpp:108; process_block launches k_rs only with one group)
@@ -3755,29 +3793,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_
   const int ta = blockIdx.y * per, tb = min(ntile, ta + per);
   __syncthreads();
   // a tile's 16 schedule entries (rows past the call repeat the last), lane l
-  // holding row l & 15, loaded from L2 two tiles ahead of their window's
-  // load (round 6: no LDS staging of the workgroup's entries, so a workgroup
-  // may take any number of tiles); row 0 / row 15 to the wave by readlane
+  // holding row l & 15, loaded from L2 during the tile before (round 6:
+  // no LDS staging of the workgroup's entries, so a workgroup may take any
+  // number of tiles); row 0 / row 15 to the wave by readlane
   auto load_e = [&](int T) __attribute__((always_inline)) {
     return sched[min(16 * T + (lane & 15), ns - 1)];
   };
   const int r = lane & 15, kk = lane >> 4; // A: row r, K column kk; B: K row kk, channel column r
-  // window loads: lane (channel lc, quarter lq) moves samples k0 + 16 lq .. + 15
+  // window loads: lane (channel lc of the group, quarter lq) moves samples
+  // k0 + 16 lq .. + 15 of group gi's row (a lane without a channel reads the
+  // group's first row and writes zeros)
   const int lc = lane >> 2, lq = lane & 3;
-  const int cl = c0 + lc;
-  const bool lcv = cl < a.C;
-  const float *mrow = a.mpx + (size_t)(lcv ? cl : c0) * a.mpx_stride; // mrow[k], 0 <= k < n
-  const float *wrow = a.win + (size_t)(lcv ? cl : c0) * 32 + 32;       // wrow[k], -32 <= k < 0
-  auto load_w = [&](const FmxSched &e, float4 (&v)[4]) __attribute__((always_inline)) {
-    rs_load_w(mrow, wrow, lcv, a.n, lq, rs_tile_k0(e), v);
+  auto load_w = [&](int gi, int k0, float4 (&v)[4]) __attribute__((always_inline)) {
+    const int cg = c0 + 16 * gi, cl = cg + lc;
+    const bool lcv = cl < a.C;
+    const size_t row = lcv ? cl : cg;
+    rs_load_w(a.mpx + row * a.mpx_stride, a.win + row * 32 + 32, lcv, a.n, lq, k0, v);
   };
-  auto store_w = [&](const FmxSched &e, int buf, const float4 (&v)[4]) __attribute__((always_inline)) {
-    rs_store_w(xs[buf][lc], lcv, a.n, lq, rs_tile_k0(e), v);
+  auto store_w = [&](int gi, int k0, int buf, const float4 (&v)[4]) __attribute__((always_inline)) {
+    rs_store_w(xs[buf][lc], c0 + 16 * gi + lc < a.C, a.n, lq, k0, v);
   };
-  auto tile = [&](int T, const FmxSched &en, int buf) __attribute__((always_inline)) {
-    const rs_f32x4 acc = rs_tile(tab, xs[buf][r], en, kk);
-    // D: lane (channel column r, output rows 4 kk .. 4 kk + 3)
-    const int cb = c0 + r;
+  // D: lane (channel column r, output rows 4 kk .. 4 kk + 3)
+  auto store_o = [&](int T, int gi, const rs_f32x4 &acc) __attribute__((always_inline)) {
+    const int cb = c0 + 16 * gi + r;
     if (cb < a.C) {
       float *dst = a.out + (size_t)cb * a.out_stride + 16 * T + 4 * kk;
       if (16 * T + 4 * kk + 3 < ns) {
@@ -3789,34 +3827,60 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_
       }
     }
   };
-  // tile T's window is loaded at tile T-2 (registers), written to LDS at the
-  // end of tile T-1: two register sets alternating (static indices)
-  // (schedule entries: tiles T, T + 1 in e0c / e1c, T + 2, T + 3 in e0n / e1n)
-  FmxSched e0c = load_e(ta), e1c = load_e(ta + 1), e0n = load_e(ta + 2), e1n = load_e(ta + 3);
+  // The workgroup walks the sequence (tile T, group gi), gi fastest, in pairs
+  // of groups: A is built once per tile and stays in registers for its groups
+  // (it depends on the schedule alone).  Step j's window is loaded into
+  // registers at step j - 2 and written to LDS in step j - 1, between that
+  // step's MFMA chain and its output stores: two register sets and the two xs
+  // buffers alternate with gi's parity (static indices).  Nothing in a step
+  // that touches memory is under a wave-level branch -- the compiler then
+  // counts the loads in flight and waits for the older set alone; with
+  // conditional loads (or the output stores ahead of the LDS write) it waits
+  // for the set it has just issued, and every step pays an L2 round trip.
+  // Pairs wholly past the last group are not walked; the odd group of the
+  // last pair and the loads past the last step run on clamped rows, write
+  // zeros to LDS and store nothing.
+  if (ta >= tb) return;
+  const int ge = (gv + 1) & ~1;
+  // schedule entries: the tile's own (ec, lane l row l & 15) are loaded during
+  // the tile before; the first window sample of the next two tiles comes from
+  // their row-0 entries alone (k0n, p0nn: one register, not a tile's entries)
+  auto load_p0 = [&](int T) __attribute__((always_inline)) { return sched[min(16 * T, ns - 1)].packed; };
+  FmxSched ec = load_e(ta);
+  int k0c = rs_tile_k0(ec), k0n = rs_k0_of(__builtin_amdgcn_readfirstlane(load_p0(ta + 1)));
   float4 wa[4], wb[4];
-  if (ta < tb) load_w(e0c, wa);
-  if (ta + 1 < tb) load_w(e1c, wb);
-  if (ta < tb) store_w(e0c, 0, wa);
-  for (int T = ta; T < tb; T += 2) {
-    if (T + 2 < tb) load_w(e0n, wa);
-    tile(T, e0c, 0);
-    if (T + 1 < tb) store_w(e1c, 1, wb);
-    if (T + 1 < tb) {
-      if (T + 3 < tb) load_w(e1n, wb);
-      tile(T + 1, e1c, 1);
-      if (T + 2 < tb) store_w(e0n, 0, wa);
+  load_w(0, k0c, wa);
+  load_w(min(1, gv - 1), k0c, wb);
+  store_w(0, k0c, 0, wa);
+  for (int T = ta; T < tb; ++T) {
+    float hv[RS_KS];
+    const int ks = rs_tile_build(tab, ec, kk, hv);
+    ec = load_e(T + 1); // (past the last tile: its last entry again)
+    const uint32_t p0nn = load_p0(T + 2);
+    for (int gi = 0; gi < ge; gi += 2) {
+      // steps j + 2, j + 3: this tile's next pair, or the next tile's first
+      const bool same = gi + 2 < ge;
+      const int ga = same ? gi + 2 : 0, k0a = same ? k0c : k0n;
+      load_w(ga, k0a, wa);
+      const rs_f32x4 acc0 = rs_tile_mma(xs[0][r], hv, ks, kk);
+      store_w(gi + 1, k0c, 1, wb);
+      store_o(T, gi, acc0);
+      load_w(min(ga + 1, gv - 1), k0a, wb);
+      const rs_f32x4 acc1 = rs_tile_mma(xs[1][r], hv, ks, kk);
+      store_w(ga, k0a, 0, wa);
+      store_o(T, gi + 1, acc1);
     }
-    e0c = e0n;
-    e1c = e1n;
-    e0n = load_e(T + 4);
-    e1n = load_e(T + 5);
+    k0c = k0n;
+    k0n = rs_k0_of(__builtin_amdgcn_readfirstlane(p0nn));
   }
 }
 
 int launch_rs(const RsArgs &a, void *stream) {
   static_assert(sizeof(RsLds) <= 17 * 1024, "k_rs LDS");
   static_assert(RS_XS >= RS_KS && RS_XP >= 4 * RS_XS && RS_XS % 4 == 0, "k_rs window layout");
-  return fmx_launch(k_rs, dim3((a.C + 15) / 16, a.parts), dim3(64), sizeof(RsLds), static_cast<hipStream_t>(stream), a);
+  if (a.gpw < 2 || (a.gpw & 1) || a.parts < 1) return FMX_E_INVALID; // k_rs alternates its window buffers by group parity
+  const int groups = (a.C + 15) / 16;
+  return fmx_launch(k_rs, dim3((groups + a.gpw - 1) / a.gpw, a.parts), dim3(64), sizeof(RsLds), static_cast<hipStream_t>(stream), a);
 }
 int launch_rds_sym(const RdsArgs &a, void *stream) {
   // two k_fe8 workgroups (2 x 62.5 KB) leave 35 KB of a CU's 160 KB: several

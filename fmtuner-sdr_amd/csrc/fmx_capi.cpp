@@ -2413,13 +2413,19 @@ struct WbBank {
   Handle *h = nullptr;
   int kind = WB_KIND_BANK;
   WbPlan p;
+  // fmx_wb_bank_create_rational at Q > 1, as Wb's: the
+  // plan is rp, the rows are [C][Q][4][Lp], a capture's history holds
+  // rp.Lh - 1 samples and a call of n outputs consumes n P / Q of every row;
+  // p carries fs, format, block, sexp, Lp and tpp
+  bool rational = false;
+  WbrPlan rp;
   int S = 0, C = 0, G = 0;    // captures, channels of all captures, groups
   std::vector<int> first;     // [S + 1]
-  uint16_t *d_w = nullptr;    // [C][4][Lp] weight rows
+  uint16_t *d_w = nullptr;    // [C][4][Lp] weight rows ([C][Q][4][Lp] on a rational bank)
   uint32_t *d_fpos = nullptr; // [C] f mod Fs
   int *d_groups = nullptr;    // [G][3] k_wbb's work list
   int *d_chan_cap = nullptr;  // [C] the capture of a channel
-  void *d_hist[2] = {};       // [S][L - 1] raw samples, the buffers taking turns (every capture advances with every call)
+  void *d_hist[2] = {};       // [S][L - 1] ([S][rp.Lh - 1]) raw samples, the buffers taking turns (every capture advances with every call)
   int cur = 0;
   WbbState *d_state = nullptr; // [S] counter and history fill: read and advanced on the device
   double *d_sp = nullptr;      // [S][4] signal parameters, written by k_wbb_set_params on sA
@@ -2447,6 +2453,10 @@ struct WbBank {
   int iq_on = 0, iq_auto = 0;      // captures out of OFF, captures in AUTO
 };
 WbBank *WBK(void *p) { return static_cast<WbBank *>(p); }
+// wide samples of every row a call of n outputs consumes (n a multiple of Q on a rational bank)
+int64_t wbb_consumed(const WbBank *b, int n) {
+  return b->rational ? static_cast<int64_t>(n) / b->rp.Q * b->rp.P : static_cast<int64_t>(n) * b->p.D;
+}
 void wbb_free(WbBank *b) {
   if (b->d_w) hipFree(b->d_w);
   if (b->d_fpos) hipFree(b->d_fpos);
@@ -2466,7 +2476,38 @@ void wbb_free(WbBank *b) {
   delete b;
 }
 
-// k_wbb and k_wbb_hist of one call on sA; the captures' state advances on the device
+// k_rbank and k_rbank_hist of one call of a rational bank: the Q phases' rows, a_r and the longest phase's history
+int rbank_launch(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float *d_out, int out_stride) {
+  const WbPlan &p = b->p;
+  const WbrPlan &q = b->rp;
+  RbankArgs a{};
+  a.in = d_wide;
+  a.wide_stride = wide_stride;
+  a.s16 = p.format == FMX_WB_S16;
+  a.P = q.P;
+  a.Q = q.Q;
+  a.Lh = q.Lh;
+  a.Lp = q.Lp;
+  a.n_out = n_out;
+  a.C = b->C;
+  a.S = b->S;
+  for (int r = 0; r < q.Q; ++r) a.a[r] = q.a[r];
+  a.w = b->d_w;
+  a.fpos = b->d_fpos;
+  a.hist = b->d_hist[b->cur];
+  a.hist_out = b->d_hist[b->cur ^ 1];
+  a.state = b->d_state;
+  a.groups = b->d_groups;
+  a.G = b->G;
+  a.fs = static_cast<uint32_t>(p.fs);
+  a.inv_fs = 1.0 / static_cast<double>(p.fs);
+  a.scale = static_cast<float>(std::ldexp(a.s16 ? 1.0 / 32768.0 : 1.0 / 255.0, -p.sexp));
+  a.out = d_out;
+  a.out_stride = out_stride;
+  return launch_rbank(a, b->h->sA);
+}
+
+// k_wbb and k_wbb_hist (k_rbank and k_rbank_hist) of one call on sA; the captures' state advances on the device
 int wbb_run(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float *d_out, int out_stride, const char *who) {
   Handle *h = b->h;
   const WbPlan &p = b->p;
@@ -2493,7 +2534,9 @@ int wbb_run(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float 
   a.out = d_out;
   a.out_stride = out_stride;
   int rc = FMX_OK;
-  if (b->iq_on == 0) {
+  if (b->rational) {
+    rc = rbank_launch(b, d_wide, wide_stride, n_out, d_out, out_stride);
+  } else if (b->iq_on == 0) {
     rc = launch_wbb(a, h->sA);
   } else { // estimator, finisher, corrected channelizer: one launch each for every capture
     const WbbIqcArgs q{b->iqc.d_blk, b->d_iq_mode, b->iqc.d_partial, b->iqc.d_tsum};
@@ -2513,40 +2556,61 @@ int wbb_run(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float 
   b->sig_pending = true;
   return FMX_OK;
 }
-} // namespace
 
-int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, const int *first_channel,
-                       const int *freq_hz, void **bank) {
+// fmx_wb_bank_create and fmx_wb_bank_create_rational (rational: wbr_plan's
+// acceptance and, at Q > 1, its plan): the table rules, the channels' rows,
+// the device buffers
+int wbb_create(void *handle, const fmx_wb_config *cfg, int n_captures, const int *first_channel, const int *freq_hz,
+               void **bank, bool rational) {
+  const std::string who = rational ? "fmx_wb_bank_create_rational: " : "fmx_wb_bank_create: ";
   Handle *h = H(handle);
   if (bank) *bank = nullptr;
   if (!h) return FMX_E_INVALID;
   if (!cfg || !first_channel || !bank) {
-    h->err = "fmx_wb_bank_create: null argument";
+    h->err = who + "null argument";
     return FMX_E_INVALID;
   }
   if (n_captures < 1 || n_captures > FMX_WBB_CAPTURES_MAX) {
-    h->err = "fmx_wb_bank_create: n_captures must be 1..1024";
+    h->err = who + "n_captures must be 1..1024";
     return FMX_E_INVALID;
   }
   bool ok = first_channel[0] == 0;
   for (int s = 0; ok && s < n_captures; ++s) ok = first_channel[s + 1] >= first_channel[s];
   const int Cn = ok ? first_channel[n_captures] : 0;
   if (!ok || (Cn > 0 && !freq_hz)) {
-    h->err = "fmx_wb_bank_create: first_channel must start at 0 and not decrease; freq_hz is required";
+    h->err = who + "first_channel must start at 0 and not decrease; freq_hz is required";
     return FMX_E_INVALID;
   }
   WbPlan p;
-  int rc = wb_plan(*cfg, &p, &h->err);
-  if (rc != FMX_OK) return rc;
+  WbrPlan q;
+  if (rational) {
+    std::string why;
+    const int rc = wbr_plan(*cfg, &q, &why);
+    if (rc != FMX_OK) { // wbr_plan's condition under this function's name
+      h->err = who + (why.rfind("fmx_wb: ", 0) == 0 ? why.substr(8) : why);
+      return rc;
+    }
+    if (q.Q == 1) return fmx_wb_bank_create(handle, cfg, n_captures, first_channel, freq_hz, bank); // an integer ratio: k_wbb's bank
+    // what the shared calls read of the integer plan; D and L stay 0 (no integer ratio)
+    p.fs = q.fs;
+    p.format = q.format;
+    p.block = q.block;
+    p.sexp = q.sexp;
+    p.Lp = q.Lp;
+    p.tpp = q.tpp;
+  } else {
+    const int rc = wb_plan(*cfg, &p, &h->err);
+    if (rc != FMX_OK) return rc;
+  }
   for (int c = 0; c < Cn; ++c)
     if (!wb_freq_ok(p, freq_hz[c])) {
-      h->err = "fmx_wb_bank_create: channel " + std::to_string(c) + " lies outside +- wide_rate / 2";
+      h->err = who + "channel " + std::to_string(c) + " lies outside +- wide_rate / 2";
       return FMX_E_INVALID;
     }
   std::vector<int> groups(static_cast<size_t>(3) * (static_cast<size_t>(n_captures) + Cn / 16 + 1));
   const int G = wbb_groups(first_channel, n_captures, groups.data(), static_cast<int>(groups.size() / 3));
   if (G < 0) {
-    h->err = "fmx_wb_bank_create: more than 65535 groups of 16 channels";
+    h->err = who + "more than 65535 groups of 16 channels";
     return G == FMX_E_CAPACITY ? FMX_E_CAPACITY : FMX_E_INVALID;
   }
   HIP_TRY(hipSetDevice(h->device));
@@ -2554,24 +2618,28 @@ int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, c
   if (!b) return FMX_E_NOMEM;
   b->h = h;
   b->p = p;
+  b->rational = rational;
+  if (rational) b->rp = q;
   b->S = n_captures;
   b->C = Cn;
   b->G = G;
   b->first.assign(first_channel, first_channel + n_captures + 1);
-  const size_t row = static_cast<size_t>(4) * p.Lp;
-  const size_t hist_bytes = static_cast<size_t>(n_captures) * (p.L - 1) * wb_sample_bytes(p);
+  const size_t row = static_cast<size_t>(4) * p.Lp * (rational ? q.Q : 1);
+  const size_t hist_bytes = static_cast<size_t>(n_captures) * (rational ? q.Lh - 1 : p.L - 1) * wb_sample_bytes(p);
   const size_t cn1 = static_cast<size_t>(std::max(Cn, 1)), g1 = static_cast<size_t>(std::max(G, 1));
   std::vector<uint16_t> rows(row * cn1);
   std::vector<uint32_t> fpos(cn1);
   std::vector<int> chan_cap(cn1);
   for (int s = 0; s < n_captures; ++s)
     for (int c = first_channel[s]; c < first_channel[s + 1]; ++c) {
-      wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
+      if (rational) wbr_weight_rows(q, freq_hz[c], rows.data() + row * c);
+      else wb_weight_rows(p, freq_hz[c], rows.data() + row * c);
       fpos[c] = wb_freq_mod(p, freq_hz[c]);
       chan_cap[c] = s;
     }
   b->iqc.tsum.assign(2 * cn1, 0.0f);
-  for (int c = 0; c < Cn; ++c) wb_tap_sums(p, rows.data() + row * c, b->iqc.tsum.data() + 2 * c);
+  if (!rational) // a rational bank has no correction
+    for (int c = 0; c < Cn; ++c) wb_tap_sums(p, rows.data() + row * c, b->iqc.tsum.data() + 2 * c);
   b->iq_mode.assign(n_captures, FMX_IQC_OFF);
   std::vector<WbbState> state(n_captures); // counter 0, nothing valid
   std::vector<double> sp(static_cast<size_t>(4) * n_captures);
@@ -2590,7 +2658,7 @@ int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, c
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_sp), sp.size() * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_sm), sm_bytes);
   if (e != hipSuccess) {
-    h->err = std::string("fmx_wb_bank_create: hipMalloc failed: ") + hipGetErrorString(e);
+    h->err = who + "hipMalloc failed: " + hipGetErrorString(e);
     wbb_free(b);
     return FMX_E_NOMEM;
   }
@@ -2609,12 +2677,23 @@ int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, c
   // the smoothers' only readers run on sA: cleared there, ahead of the first of them
   if (e == hipSuccess) e = hipMemsetAsync(b->d_sm, 0, sm_bytes, h->sA);
   if (e != hipSuccess) {
-    h->err = std::string("fmx_wb_bank_create: ") + hipGetErrorString(e);
+    h->err = who + hipGetErrorString(e);
     wbb_free(b);
     return FMX_E_HIP;
   }
   *bank = b;
   return FMX_OK;
+}
+} // namespace
+
+int fmx_wb_bank_create(void *handle, const fmx_wb_config *cfg, int n_captures, const int *first_channel,
+                       const int *freq_hz, void **bank) {
+  return wbb_create(handle, cfg, n_captures, first_channel, freq_hz, bank, false);
+}
+
+int fmx_wb_bank_create_rational(void *handle, const fmx_wb_config *cfg, int n_captures, const int *first_channel,
+                                const int *freq_hz, void **bank) {
+  return wbb_create(handle, cfg, n_captures, first_channel, freq_hz, bank, true);
 }
 
 int fmx_wb_bank_destroy(void *bank) {
@@ -2634,20 +2713,22 @@ int fmx_wb_bank_set_freq(void *bank, int channel, int freq_hz) {
     return FMX_E_INVALID;
   }
   if (b->ev_set) HIP_TRY(hipEventSynchronize(b->ev)); // the staging image's last copy has left it
-  const size_t row = static_cast<size_t>(4) * b->p.Lp;
-  wb_weight_rows(b->p, freq_hz, b->stage);
+  const size_t row = static_cast<size_t>(4) * b->p.Lp * (b->rational ? b->rp.Q : 1);
+  if (b->rational) wbr_weight_rows(b->rp, freq_hz, b->stage);
+  else wb_weight_rows(b->p, freq_hz, b->stage);
   const uint32_t fm = wb_freq_mod(b->p, freq_hz);
   std::memcpy(b->stage + row, &fm, sizeof(fm));
   // on the stage stream: after the calls queued so far, before later ones
   HIP_TRY(hipMemcpyAsync(b->d_w + row * channel, b->stage, row * sizeof(uint16_t), hipMemcpyHostToDevice, h->sA));
   HIP_TRY(hipMemcpyAsync(b->d_fpos + channel, b->stage + row, sizeof(uint32_t), hipMemcpyHostToDevice, h->sA));
-  // the channel's tap sums follow its rows (behind f mod Fs in the staging image)
-  float *ts = b->iqc.tsum.data() + 2 * static_cast<size_t>(channel);
-  wb_tap_sums(b->p, b->stage, ts);
-  if (b->iqc.d_tsum) {
-    std::memcpy(b->stage + row + 2, ts, 2 * sizeof(float));
-    HIP_TRY(hipMemcpyAsync(b->iqc.d_tsum + 2 * static_cast<size_t>(channel), b->stage + row + 2, 2 * sizeof(float),
-                           hipMemcpyHostToDevice, h->sA));
+  if (!b->rational) { // the channel's tap sums follow its rows (behind f mod Fs in the staging image)
+    float *ts = b->iqc.tsum.data() + 2 * static_cast<size_t>(channel);
+    wb_tap_sums(b->p, b->stage, ts);
+    if (b->iqc.d_tsum) {
+      std::memcpy(b->stage + row + 2, ts, 2 * sizeof(float));
+      HIP_TRY(hipMemcpyAsync(b->iqc.d_tsum + 2 * static_cast<size_t>(channel), b->stage + row + 2, 2 * sizeof(float),
+                             hipMemcpyHostToDevice, h->sA));
+    }
   }
   HIP_TRY(hipEventRecord(b->ev, h->sA));
   b->ev_set = true;
@@ -2685,8 +2766,13 @@ int fmx_wb_bank_process(void *bank, const void *d_wide, size_t wide_stride, int 
     h->err = "fmx_wb_bank_process: n_out exceeds the object's block";
     return FMX_E_CAPACITY;
   }
-  if (wide_stride < static_cast<size_t>(n_out) * static_cast<size_t>(p.D)) {
-    h->err = "fmx_wb_bank_process: wide_stride is less than n_out * D samples";
+  if (b->rational && n_out % b->rp.Q != 0) {
+    h->err = "fmx_wb_bank_process: n_out must be a multiple of Q = " + std::to_string(b->rp.Q) + " (wide_rate / dsp_rate = P / Q)";
+    return FMX_E_INVALID;
+  }
+  if (wide_stride < static_cast<size_t>(wbb_consumed(b, n_out))) {
+    h->err = b->rational ? "fmx_wb_bank_process: wide_stride is less than n_out * P / Q samples"
+                         : "fmx_wb_bank_process: wide_stride is less than n_out * D samples";
     return FMX_E_INVALID;
   }
   if (n_out == 0) return FMX_OK;
@@ -2702,14 +2788,25 @@ int fmx_wb_bank_process_block(void *bank, const void *d_wide, size_t wide_stride
   const WbPlan &p = b->p;
   const char *bad = nullptr;
   if (h->M != 1) bad = "the handle's iq_rate must equal its dsp_rate";
-  else if (p.fs / p.D != h->cfg.dsp_rate) bad = "the bank's dsp_rate is not the handle's";
+  else if (b->rational ? static_cast<int64_t>(p.fs) * b->rp.Q != static_cast<int64_t>(h->cfg.dsp_rate) * b->rp.P
+                       : p.fs / p.D != h->cfg.dsp_rate)
+    bad = "the bank's dsp_rate is not the handle's";
   else if (b->C != h->C) bad = "the bank's channel total is not the handle's channel count";
   else if (n < 0 || (n > 0 && !d_wide)) bad = "null input or negative n";
   else if (!o || !o->d_pcm_l || !o->d_pcm_r || !o->d_pcm_count) bad = "d_pcm_l, d_pcm_r and d_pcm_count are required";
   else if (o->d_signal) bad = "d_signal must be NULL (fmx_wb_bank_signal, called behind this call, delivers every station's RF level)";
-  else if (n > 0 && wide_stride < static_cast<size_t>(n) * static_cast<size_t>(p.D)) bad = "wide_stride is less than n * D samples";
+  else if (n > 0 && !b->rational && wide_stride < static_cast<size_t>(n) * static_cast<size_t>(p.D))
+    bad = "wide_stride is less than n * D samples";
   if (bad) {
     h->err = std::string("fmx_wb_bank_process_block: ") + bad;
+    return FMX_E_INVALID;
+  }
+  if (b->rational && n % b->rp.Q != 0) {
+    h->err = "fmx_wb_bank_process_block: n must be a multiple of Q = " + std::to_string(b->rp.Q) + " (wide_rate / dsp_rate = P / Q)";
+    return FMX_E_INVALID;
+  }
+  if (b->rational && wide_stride < static_cast<size_t>(wbb_consumed(b, n))) {
+    h->err = "fmx_wb_bank_process_block: wide_stride is less than n * P / Q samples";
     return FMX_E_INVALID;
   }
   if (n > std::min(h->cfg.block, p.block)) {
@@ -2772,7 +2869,7 @@ int fmx_wb_bank_signal(void *bank, fmx_signal_level *d_level) {
   }
   HIP_TRY(hipSetDevice(h->device));
   if (!b->d_clip) {
-    const size_t n_clip = static_cast<size_t>(b->S) * wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D) * 2;
+    const size_t n_clip = static_cast<size_t>(b->S) * wb_scan_clip_workgroups(static_cast<long>(wbb_consumed(b, p.block))) * 2;
     if (hipMalloc(reinterpret_cast<void **>(&b->d_clip), n_clip * sizeof(uint32_t)) != hipSuccess) {
       b->d_clip = nullptr;
       h->err = "fmx_wb_bank_signal: hipMalloc failed";
@@ -2790,6 +2887,7 @@ int fmx_wb_bank_signal(void *bank, fmx_signal_level *d_level) {
   a.wide_stride = b->sig_wstride;
   a.s16 = p.format == FMX_WB_S16;
   a.D = p.D;
+  if (b->rational) a.n_in = static_cast<long>(wbb_consumed(b, b->sig_n)); // every capture's n P / Q raw samples
   a.clip = b->d_clip;
   a.chan_cap = b->d_chan_cap;
   a.sm = b->d_sm;
@@ -3133,6 +3231,10 @@ WbBank *iqc_bank(void *bank, const char *who) {
   if (!b) return nullptr;
   if (b->kind != WB_KIND_BANK) {
     b->h->err = std::string(who) + ": not a capture bank";
+    return nullptr;
+  }
+  if (b->rational) {
+    b->h->err = std::string(who) + ": a bank of fmx_wb_bank_create_rational at Q > 1 has no IQ correction (out of scope)";
     return nullptr;
   }
   return b;

@@ -495,8 +495,35 @@ struct WbbLevelArgs {
   fmx_signal_level *level; // [C]
   const double *sp;        // [S][4] gain*factor, bias, floor, ceil of each capture (device)
   int nclip;               // set by the launcher
+  long n_in;               // a capture's raw samples of the call when they are not n * D (a rational bank: n P / Q; D is then unused); 0: n * D
 };
 int launch_wbb_level(const WbbLevelArgs &a, void *stream);
+
+// ---- the bank at rational rates (fmx_wb_bank_rational.inc) ----
+// k_wbr's tile list (grid.x) over k_wbb's group table (grid.y): WbrArgs with
+// in, hist, valid and base_mod per capture, as WbbArgs has them
+struct RbankArgs {
+  const void *in;          // [S][wide_stride] wide samples; n_out P / Q of each row are read
+  size_t wide_stride;      // samples
+  int s16, in_al;          // as WbArgs
+  int P, Q, Lh, Lp, n_out, C, S; // n_out a multiple of Q; C: the channels of all captures
+  int a[FMX_WBR_QMAX];     // a_r
+  const uint16_t *w;       // [C][Q][4][Lp] weight rows
+  const uint32_t *fpos;    // [C] f mod Fs
+  const void *hist;        // [S][Lh - 1] raw samples before this call
+  void *hist_out;          // the same after it (another buffer)
+  WbbState *state;         // [S]
+  const int *groups;       // [G][3] as WbbArgs
+  int G;
+  uint32_t fs;
+  double inv_fs;
+  float scale;
+  float *out;
+  int out_stride;
+  int nt, ntiles;          // as WbrArgs (set by the launcher)
+  long n_in;               // n_out P / Q (set by the launcher)
+};
+int launch_rbank(const RbankArgs &a, void *stream); // k_rbank, then k_rbank_hist (which advances the state)
 
 // ---- the bank's DC / IQ-imbalance correction (fmx_wb_bank_iqc.inc) ----
 // one capture's mode and smoothing, kept on the device beside its FmxIqcBlock:

@@ -3956,6 +3956,7 @@ int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sa
 #include "fmx_wb_level.inc"
 #include "fmx_wb_bank.inc"
 #include "fmx_wb_rational.inc"
+#include "fmx_wb_bank_rational.inc"
 #include "fmx_wb_iqc.inc"
 #include "fmx_wb_bank_iqc.inc"
 #include "fmx_fecf.inc"

@@ -145,10 +145,11 @@ int launch_wbb_set_params(double *sp, int S, int capture, const double *v, void 
 }
 
 /* ---- the bank's RF level (fmx_wb_bank_signal): k_wb_scan_clip and k_wb_level with a capture dimension ---- */
-// the same 2048 samples per workgroup over row blockIdx.y of the call's input:
-// the counts to clip[capture][workgroup][2]
+// the same 2048 samples per workgroup over the n_in raw samples (n D, or a
+// rational bank's n P / Q) of row blockIdx.y of the call's input: the counts
+// to clip[capture][workgroup][2]
 template <typename T> __global__ __launch_bounds__(256) void k_wbb_clip(WbbLevelArgs a) {
-  wb_clip_count(static_cast<const T *>(a.in) + 2 * (size_t)blockIdx.y * a.wide_stride, (long)a.n * a.D,
+  wb_clip_count(static_cast<const T *>(a.in) + 2 * (size_t)blockIdx.y * a.wide_stride, a.n_in,
                 a.clip + 2 * ((size_t)blockIdx.y * a.nclip + blockIdx.x));
 }
 
@@ -159,16 +160,18 @@ template <int W> __global__ __launch_bounds__(256) void k_wbb_level(WbbLevelArgs
   if (threadIdx.x != 0) return;
   const int cap = a.chan_cap[c];
   a.level[c] = wb_level_record(sum, 1.0, (double)a.n, a.clip + 2 * (size_t)cap * a.nclip, a.nclip,
-                               (double)((long)a.n * a.D), a.sp + 4 * (size_t)cap, a.sm + 2 * (size_t)c);
+                               (double)a.n_in, a.sp + 4 * (size_t)cap, a.sm + 2 * (size_t)c);
 }
 
 int launch_wbb_level(const WbbLevelArgs &a0, void *stream) {
   WbbLevelArgs a = a0;
-  if (a.C <= 0 || a.S <= 0 || a.n <= 0 || a.stride < a.n || a.D < 1 || !a.rows || !a.in || !a.clip || !a.sm || !a.level ||
-      !a.chan_cap || !a.sp || a.wide_stride < (size_t)a.n * (size_t)a.D)
+  if (a.C <= 0 || a.S <= 0 || a.n <= 0 || a.stride < a.n || (a.n_in == 0 && a.D < 1) || a.n_in < 0 || !a.rows || !a.in ||
+      !a.clip || !a.sm || !a.level || !a.chan_cap || !a.sp)
     return FMX_E_INVALID;
+  if (a.n_in == 0) a.n_in = (long)a.n * a.D; // else a rational bank's call: n P / Q raw samples of every row
+  if (a.wide_stride < (size_t)a.n_in) return FMX_E_INVALID;
   if ((reinterpret_cast<uintptr_t>(a.rows) & 3) || (reinterpret_cast<uintptr_t>(a.level) & 7)) return FMX_E_INVALID;
-  a.nclip = wb_scan_clip_workgroups((long)a.n * a.D);
+  a.nclip = wb_scan_clip_workgroups(a.n_in);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 cgrid((unsigned)a.nclip, (unsigned)a.S);
   if (a.s16) hipLaunchKernelGGL(k_wbb_clip<int16_t>, cgrid, dim3(256), 0, st, a);

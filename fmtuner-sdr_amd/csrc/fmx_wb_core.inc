@@ -1,7 +1,7 @@
 /* ================================================================== */
 /* The wideband family's shared pieces (DESIGN.md section 25): what     */
-/* k_wb, k_wb_scan, k_wbb, k_wbr, k_wb_iqc, k_wb_scan_iqc and the level */
-/* and clip kernels are put together from                               */
+/* k_wb, k_wb_scan, k_wbb, k_wbr, k_rbank, k_wb_iqc, k_wb_scan_iqc and  */
+/* the level and clip kernels are put together from                     */
 /* ================================================================== */
 /* y_c[n] = e^{-j theta_c(i0)} sum_k W_c[k] x[i0 - k], W_c[k] = 2 fc h[k]
  * e^{+j 2 pi f_c k / Fs}, i0 the wide sample output n ends at: a complex GEMM

@@ -135,6 +135,7 @@ def lib():
         "fmx_wb_signal_reset": (i, [vp, i]),
         "fmx_diag_lds_bytes": (i, [i]),
         "fmx_wb_bank_create": (i, [vp, C.POINTER(WbConfig), i, C.POINTER(i), C.POINTER(i), C.POINTER(vp)]),
+        "fmx_wb_bank_create_rational": (i, [vp, C.POINTER(WbConfig), i, C.POINTER(i), C.POINTER(i), C.POINTER(vp)]),
         "fmx_wb_bank_destroy": (i, [vp]),
         "fmx_wb_bank_set_freq": (i, [vp, i, i]),
         "fmx_wb_bank_reset": (i, [vp, i, C.c_int64]),
@@ -454,9 +455,12 @@ class WidebandBank:
     captures of one configuration, capture s with the channels freq_hz[s] (a
     list, possibly empty), channelized by one launch.  The bank's channels
     are the captures' in order; d_wide is [captures][wide_stride] samples.
-    Close it before its handle."""
+    Close it before its handle.  rational: create it with
+    fmx_wb_bank_create_rational (wide_rate / dsp_rate = P / Q; every call's
+    output count is then a multiple of Q and consumes n P / Q samples of
+    every row)."""
 
-    def __init__(self, handle, wcfg, freq_hz):
+    def __init__(self, handle, wcfg, freq_hz, rational=False):
         self.L = lib()
         self.handle = handle
         self.cfg = wcfg
@@ -469,10 +473,13 @@ class WidebandBank:
         first = (C.c_int * (self.captures + 1))(*self.first)
         f = (C.c_int * max(self.n, 1))(*flat)
         b = C.c_void_p()
-        rc = self.L.fmx_wb_bank_create(handle.h, C.byref(wcfg), self.captures, first, f, C.byref(b))
+        name = "fmx_wb_bank_create_rational" if rational else "fmx_wb_bank_create"
+        rc = getattr(self.L, name)(handle.h, C.byref(wcfg), self.captures, first, f, C.byref(b))
         self.b = b if rc == FMX_OK else None
         if rc != FMX_OK:
-            raise FmxError(f"fmx_wb_bank_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+            raise FmxError(f"{name} failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+        # wide samples of every row per output: D, or P / Q of a rational bank
+        self.ratio = wb_ratio(wcfg)[:2] if rational else (wcfg.wide_rate // wcfg.dsp_rate, 1)
 
     def _ck(self, rc, what):
         if rc != FMX_OK:
@@ -497,18 +504,27 @@ class WidebandBank:
         self._ck(self.L.fmx_wb_bank_reset(self.b, capture, sample0), "fmx_wb_bank_reset")
 
     def process(self, d_wide, wide_stride, n_out, d_out, out_stride):
-        """d_wide: [captures][wide_stride] interleaved I/Q samples, n_out * D of
-        each row read; d_out: [n][out_stride] complex float."""
+        """d_wide: [captures][wide_stride] interleaved I/Q samples, n_out * D
+        (a rational bank: n_out * P / Q, see consumed) of each row read;
+        d_out: [n][out_stride] complex float."""
         self._ck(self.L.fmx_wb_bank_process(self.b, C.c_void_p(d_wide), wide_stride, n_out, C.c_void_p(d_out),
                                             out_stride), "fmx_wb_bank_process")
 
+    def consumed(self, n):
+        """Wide samples of every row a call of n outputs reads: n * D, or
+        n * P / Q of a rational bank (n a multiple of Q)."""
+        P, Q = self.ratio
+        return n // Q * P
+
     def process_block(self, d_wide, wide_stride, n, out):
-        """fmx_wb_bank_process_block: Wideband.process_block for every capture's stations."""
+        """fmx_wb_bank_process_block: Wideband.process_block for every
+        capture's stations; consumed(n) samples of each row are read."""
         self._ck(self.L.fmx_wb_bank_process_block(self.b, C.c_void_p(d_wide), wide_stride, n, C.byref(out)),
                  "fmx_wb_bank_process_block")
 
     def signal(self, d_level):
-        """fmx_wb_bank_signal: Wideband.signal for every channel of the bank."""
+        """fmx_wb_bank_signal: Wideband.signal for every channel of the bank;
+        the clip ratios are those of the capture's consumed(n) raw samples."""
         self._ck(self.L.fmx_wb_bank_signal(self.b, C.c_void_p(d_level)), "fmx_wb_bank_signal")
 
     def set_signal_params(self, capture=-1, applied_gain_db=0, gain_comp_factor=0.5, bias_db=-4.0, floor_dbfs=-55.0,

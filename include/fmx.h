@@ -47,7 +47,9 @@
 extern "C" {
 #endif
 
-/* ABI history: the bank's correction per capture (fmx_wb_bank_set_iq_correction, fmx_wb_bank_iq_correction) arrived at 13
+/* ABI history: the capture bank at rational rates (fmx_wb_bank_create_rational: many 2.048, 10 or 20 MS/s captures
+ * channelized at P / Q in one call) arrived at 13 without a bump, as the bank and the rational rates did: an addition only;
+ * the bank's correction per capture (fmx_wb_bank_set_iq_correction, fmx_wb_bank_iq_correction) arrived at 13
  * without a bump: additions only; the DC / IQ-imbalance correction (fmx_wb_set_iq_correction, fmx_wb_iq_correction,
  * fmx_wb_scan_set_iq_correction, fmx_wb_scan_iq_correction, fmx_iq_estimate, fmx_iq_correction, FMX_IQC_*)
  * arrived at 13 without a bump, as the bank and the rational rates did: additions only; rational wide rates (fmx_wb_create_rational, fmx_wb_ratio, fmx_wb_weights_rational,
@@ -361,8 +363,9 @@ int fmx_wb_weights(const fmx_wb_config *cfg, int freq_hz, float *out, int cap);
  * dsp_rate P (the fast front end still needs n >= 1024 and n % 4 == 0, e.g.
  * n = 4092 at Q = 3); fmx_wb_signal's clip ratios are over the call's n P / Q
  * raw samples; the history holds ceil(Lup / Q) - 1 raw samples.
- * Out of scope: the capture bank and the band scan stay integer (the scan's
- * dsp_rate is free, so a 20 MS/s scan at 200 kHz needs no rational plan); and
+ * Out of scope: the band scan stays integer (the scan's dsp_rate is free, so
+ * a 20 MS/s scan at 200 kHz needs no rational plan; the capture bank takes
+ * P / Q through fmx_wb_bank_create_rational below); and
  * there is no int8 format -- a HackRF caller flips bit 7 of each byte and
  * passes FMX_WB_U8.  These symbols arrived without a bump of FMX_ABI_VERSION
  * (see above). */
@@ -430,6 +433,37 @@ int fmx_wb_bank_signal_reset(void *bank, int channel /* -1: all */);
  * for more than 65 535 groups; -G, with nothing written, when cap < G or out
  * is NULL (n_captures + first_channel[n_captures] / 16 groups always do). */
 int fmx_wb_bank_groups(const int *first_channel, int n_captures, int *out, int cap);
+
+/* ---- capture bank at rational rates: wide_rate / dsp_rate = P / Q for every capture ----
+ * fmx_wb_bank_create refuses a wide_rate that is no multiple of dsp_rate;
+ * fmx_wb_bank_create_rational takes what fmx_wb_create_rational takes (Q <= 16,
+ * 2 <= P / Q <= 128, one tile's window within 80 KB for the format) and
+ * refuses the rest with FMX_E_INVALID, the message naming this function and
+ * the condition; the table rules are fmx_wb_bank_create's.  With Q = 1 it is
+ * fmx_wb_bank_create (the same object, rows bit for bit).  The result is a
+ * bank: fmx_wb_bank_destroy, _set_freq, _reset, _process, _process_block,
+ * _signal, _set_signal_params and _signal_reset take it, and capture s behaves
+ * as an fmx_wb_create_rational object with the same configuration and the
+ * frequencies freq_hz[first_channel[s] .. first_channel[s + 1]), fed row s:
+ * output rows, the history of ceil(Lup / Q) - 1 raw samples, the 64-bit
+ * counter, the ordering of set_freq on the stage stream, n == 0 and the
+ * "measured once" rule of the level call, bit for bit.  One launch channelizes
+ * every capture.  What differs from the integer bank at
+ * Q > 1: n_out (n of fmx_wb_bank_process_block) must be a multiple of Q, else
+ * FMX_E_INVALID with a message naming the function and Q; block need not be a
+ * multiple.  A call consumes n_out P / Q wide samples of every row:
+ * wide_stride >= n_out P / Q, else FMX_E_INVALID; samples of a row past that
+ * are never read.  fmx_wb_bank_process_block's rate condition is
+ * wide_rate Q == dsp_rate P, in 64 bits.  fmx_wb_bank_signal's clip ratios are
+ * those of the capture's own n P / Q raw samples.
+ * fmx_wb_bank_set_iq_correction and fmx_wb_bank_iq_correction on such a bank
+ * return FMX_E_INVALID with a message naming the function, as the single
+ * rational object's calls do: the correction at rational rates is out of
+ * scope, as are mixed rates within one bank.
+ * This symbol arrived without a bump of FMX_ABI_VERSION (see above). */
+int fmx_wb_bank_create_rational(void *handle, const fmx_wb_config *cfg, int n_captures,
+                                const int *first_channel /* [n_captures + 1] */,
+                                const int *freq_hz /* [first_channel[n_captures]] */, void **bank);
 
 /* ---- band scan: the RF level of every scan point from one wide capture ----
  * The reference's scan (main.cpp:1064-1121: retune, three reads,

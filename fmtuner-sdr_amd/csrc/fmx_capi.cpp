@@ -1922,10 +1922,10 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
 
 /* ---- wideband channelizer (fmx.h; design in fmx_wb_design.cpp, kernel in fmx_wb.inc) ---- */
 namespace {
-// The first two members of Wb, WbBank and WbScan are alike, so that a call
-// handed the wrong kind of object (fmx_wb_set_iq_correction on a bank) can
-// tell and refuse.
-enum WbKind { WB_KIND_WB = 0x5742, WB_KIND_BANK = 0x5743, WB_KIND_SCAN = 0x5744 };
+// The first two members of Wb, WbBank, WbScan and WbBankScan are alike, so
+// that a call handed the wrong kind of object (fmx_wb_set_iq_correction on a
+// bank) can tell and refuse.
+enum WbKind { WB_KIND_WB = 0x5742, WB_KIND_BANK = 0x5743, WB_KIND_SCAN = 0x5744, WB_KIND_BSCAN = 0x5745 };
 // DC / IQ-imbalance correction of one object (fmx.h; kernels in fmx_wb_iqc.inc,
 // DESIGN.md section 24).  Nothing is allocated or launched while the mode has
 // never left FMX_IQC_OFF.
@@ -3091,6 +3091,254 @@ int fmx_wb_scan_process(void *scan, const void *d_wide, int n_out, fmx_signal_le
   }
   if (rc != FMX_OK) {
     h->err = "fmx_wb_scan_process: kernel launch failed";
+    return rc;
+  }
+  return FMX_OK;
+}
+
+/* ---- band scan over a capture bank (fmx.h; kernels in fmx_wb_bank_scan.inc) ---- */
+namespace {
+struct WbBankScan {
+  Handle *h = nullptr;
+  int kind = WB_KIND_BSCAN;
+  WbPlan p;
+  int S = 0, P = 0, G = 0;    // captures, points of all captures, work-list entries
+  std::vector<int> first;     // [S + 1]
+  std::vector<int> groups;    // [G][3] the work list as the device holds it
+  uint16_t *d_w = nullptr;    // [P][4][Lp] weight rows
+  int *d_groups = nullptr;    // [G][3]
+  int *d_pt_slot = nullptr;   // [P] 16 (4 entry + wave) + column
+  int *d_pt_cap = nullptr;    // [P] the capture of a point
+  float *d_partial = nullptr; // [4 G][workgroups of a full block][16]
+  uint32_t *d_clip = nullptr; // [S][clip workgroups of a full block][2]
+  float *d_sm = nullptr;      // [P][2] level smoothers
+  double *d_sp = nullptr;     // [S][4] signal parameters, written by k_wbb_set_params on sA
+};
+void bscan_free(WbBankScan *b) {
+  if (b->d_w) hipFree(b->d_w);
+  if (b->d_groups) hipFree(b->d_groups);
+  if (b->d_pt_slot) hipFree(b->d_pt_slot);
+  if (b->d_pt_cap) hipFree(b->d_pt_cap);
+  if (b->d_partial) hipFree(b->d_partial);
+  if (b->d_clip) hipFree(b->d_clip);
+  if (b->d_sm) hipFree(b->d_sm);
+  if (b->d_sp) hipFree(b->d_sp);
+  delete b;
+}
+// the object behind an fmx_wb_bank_scan_* call, or NULL (with the handle's message set when there is an object)
+WbBankScan *BSC(void *p, const char *who) {
+  WbBankScan *b = static_cast<WbBankScan *>(p);
+  if (!b) return nullptr;
+  if (b->kind != WB_KIND_BSCAN) {
+    b->h->err = std::string(who) + ": not an fmx_wb_bank_scan object";
+    return nullptr;
+  }
+  return b;
+}
+} // namespace
+
+int fmx_wb_bank_scan_create(void *handle, const fmx_wb_config *cfg, int n_captures, const int *first_point,
+                            const int *freq_hz, void **bscan) {
+  const std::string who = "fmx_wb_bank_scan_create: ";
+  Handle *h = H(handle);
+  if (bscan) *bscan = nullptr;
+  if (!h) return FMX_E_INVALID;
+  if (!cfg || !first_point || !freq_hz || !bscan) {
+    h->err = who + "null argument";
+    return FMX_E_INVALID;
+  }
+  if (n_captures < 1 || n_captures > FMX_WBB_CAPTURES_MAX) {
+    h->err = who + "n_captures must be 1..1024";
+    return FMX_E_INVALID;
+  }
+  bool ok = first_point[0] == 0;
+  for (int s = 0; ok && s < n_captures; ++s) ok = first_point[s + 1] >= first_point[s];
+  if (!ok) {
+    h->err = who + "first_point must start at 0 and not decrease";
+    return FMX_E_INVALID;
+  }
+  const int Pn = first_point[n_captures];
+  if (Pn < 1 || Pn > FMX_BSCAN_POINTS_MAX) {
+    h->err = who + "the captures' points must be 1..8192 in all";
+    return FMX_E_INVALID;
+  }
+  // the plan is the single scan's wb part: wb_scan_plan runs this on cfg.wb
+  WbPlan p;
+  int rc = wb_plan(*cfg, &p, &h->err);
+  if (rc != FMX_OK) return rc;
+  const int s16 = p.format == FMX_WB_S16;
+  const int nt = wb_scan_tiles(p.D, p.Lp, s16);
+  if (nt < 1 || p.block <= p.tpp) {
+    h->err = who + "block must exceed taps_per_phase";
+    return FMX_E_INVALID;
+  }
+  for (int k = 0; k < Pn; ++k)
+    if (!wb_freq_ok(p, freq_hz[k])) {
+      h->err = who + "point " + std::to_string(k) + " lies outside +- wide_rate / 2";
+      return FMX_E_INVALID;
+    }
+  std::vector<int> groups(static_cast<size_t>(3) * (static_cast<size_t>(n_captures) + Pn / 64 + 1));
+  const int G = bscan_groups(first_point, n_captures, groups.data(), static_cast<int>(groups.size() / 3));
+  if (G < 1) {
+    h->err = who + "bad point table";
+    return FMX_E_INVALID;
+  }
+  groups.resize(static_cast<size_t>(3) * G);
+  HIP_TRY(hipSetDevice(h->device));
+  WbBankScan *b = new (std::nothrow) WbBankScan();
+  if (!b) return FMX_E_NOMEM;
+  b->h = h;
+  b->p = p;
+  b->S = n_captures;
+  b->P = Pn;
+  b->G = G;
+  b->first.assign(first_point, first_point + n_captures + 1);
+  b->groups = groups;
+  const size_t row = static_cast<size_t>(4) * p.Lp;
+  std::vector<uint16_t> rows(row * Pn);
+  for (int k = 0; k < Pn; ++k) wb_weight_rows(p, freq_hz[k], rows.data() + row * k);
+  // where a point's partials lie and whose clip counts and parameters it takes
+  std::vector<int> pt_slot(Pn), pt_cap(Pn);
+  for (int e = 0; e < G; ++e)
+    for (int q = 0; q < groups[3 * e + 2]; ++q) {
+      const int k = groups[3 * e + 1] + q;
+      pt_slot[k] = 16 * (4 * e + q / 16) + q % 16;
+      pt_cap[k] = groups[3 * e];
+    }
+  std::vector<double> sp(static_cast<size_t>(4) * n_captures);
+  for (int s = 0; s < n_captures; ++s) {
+    const double def[4] = {0.0, -4.0, -55.0, -19.0}; // gain*factor, bias, floor, ceil
+    for (int k = 0; k < 4; ++k) sp[4 * s + k] = def[k];
+  }
+  const size_t n_partial = static_cast<size_t>(4) * G * wb_scan_workgroups(p.block, p.tpp, nt) * 16;
+  const size_t n_clip = static_cast<size_t>(n_captures) * wb_scan_clip_workgroups(static_cast<long>(p.block) * p.D) * 2;
+  const size_t sm_bytes = static_cast<size_t>(Pn) * 2 * sizeof(float);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_w), rows.size() * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_groups), groups.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_pt_slot), pt_slot.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_pt_cap), pt_cap.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_partial), n_partial * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_clip), n_clip * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_sm), sm_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_sp), sp.size() * sizeof(double));
+  if (e != hipSuccess) {
+    h->err = who + "hipMalloc failed: " + hipGetErrorString(e);
+    bscan_free(b);
+    return FMX_E_NOMEM;
+  }
+  // synchronous: the tables are complete before the first call is queued
+  e = hipMemcpy(b->d_w, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_groups, groups.data(), groups.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_pt_slot, pt_slot.data(), pt_slot.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_pt_cap, pt_cap.data(), pt_cap.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_sp, sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(b->d_sm, 0, sm_bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    h->err = who + hipGetErrorString(e);
+    bscan_free(b);
+    return FMX_E_HIP;
+  }
+  *bscan = b;
+  return FMX_OK;
+}
+
+int fmx_wb_bank_scan_destroy(void *bscan) {
+  WbBankScan *b = BSC(bscan, "fmx_wb_bank_scan_destroy");
+  if (!b) return FMX_E_INVALID;
+  if (b->h->sA) hipStreamSynchronize(b->h->sA);
+  bscan_free(b);
+  return FMX_OK;
+}
+
+int fmx_wb_bank_scan_set_signal_params(void *bscan, int capture, int applied_gain_db, double gain_comp_factor,
+                                       double bias_db, double floor_dbfs, double ceil_dbfs) {
+  WbBankScan *b = BSC(bscan, "fmx_wb_bank_scan_set_signal_params");
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (capture < -1 || capture >= b->S) {
+    h->err = "fmx_wb_bank_scan_set_signal_params: capture out of range";
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // computeSignalLevel: compensated = (dbfs - gain * factor) + bias; a one-thread kernel on sA carries the values
+  const double v[4] = {static_cast<double>(applied_gain_db) * gain_comp_factor, bias_db, floor_dbfs, ceil_dbfs};
+  int rc;
+  if ((rc = launch_wbb_set_params(b->d_sp, b->S, capture, v, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_bank_scan_set_signal_params: kernel launch failed";
+    return rc;
+  }
+  return FMX_OK;
+}
+
+int fmx_wb_bank_scan_reset(void *bscan, int capture) {
+  WbBankScan *b = BSC(bscan, "fmx_wb_bank_scan_reset");
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  if (capture < -1 || capture >= b->S) {
+    h->err = "fmx_wb_bank_scan_reset: capture out of range";
+    return FMX_E_INVALID;
+  }
+  int rc;
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  // a capture's smoothers are contiguous; on sA: behind the calls queued so far, ahead of later ones
+  const int p0 = capture < 0 ? 0 : b->first[capture], p1 = capture < 0 ? b->P : b->first[capture + 1];
+  if (p1 > p0)
+    HIP_TRY(hipMemsetAsync(b->d_sm + 2 * static_cast<size_t>(p0), 0, static_cast<size_t>(p1 - p0) * 2 * sizeof(float), h->sA));
+  return FMX_OK;
+}
+
+int fmx_wb_bank_scan_process(void *bscan, const void *d_wide, size_t wide_stride, int n_out, fmx_signal_level *d_level) {
+  WbBankScan *b = BSC(bscan, "fmx_wb_bank_scan_process");
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  const WbPlan &p = b->p;
+  if (!d_wide || !d_level) {
+    h->err = "fmx_wb_bank_scan_process: null buffer";
+    return FMX_E_INVALID;
+  }
+  if (reinterpret_cast<uintptr_t>(d_level) & 7) {
+    h->err = "fmx_wb_bank_scan_process: d_level is not 8-byte aligned";
+    return FMX_E_INVALID;
+  }
+  if (n_out <= p.tpp) {
+    h->err = "fmx_wb_bank_scan_process: n_out must exceed taps_per_phase (the outputs before it are left out)";
+    return FMX_E_INVALID;
+  }
+  if (n_out > p.block) {
+    h->err = "fmx_wb_bank_scan_process: n_out exceeds the object's block";
+    return FMX_E_CAPACITY;
+  }
+  if (wide_stride < static_cast<size_t>(n_out) * static_cast<size_t>(p.D)) {
+    h->err = "fmx_wb_bank_scan_process: wide_stride is less than n_out * D samples";
+    return FMX_E_INVALID;
+  }
+  int rc;
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  BscanArgs a{};
+  a.in = d_wide;
+  a.wide_stride = wide_stride;
+  a.s16 = p.format == FMX_WB_S16;
+  a.D = p.D;
+  a.tpp = p.tpp;
+  a.Lp = p.Lp;
+  a.n_out = n_out;
+  a.P = b->P;
+  a.S = b->S;
+  a.w = b->d_w;
+  a.groups = b->d_groups;
+  a.G = b->G;
+  a.pt_slot = b->d_pt_slot;
+  a.pt_cap = b->d_pt_cap;
+  a.partial = b->d_partial;
+  a.clip = b->d_clip;
+  a.sm = b->d_sm;
+  a.level = d_level;
+  // raw integers (2 b - 255 for u8) times weights * 2^sexp, squared
+  a.pscale = std::ldexp(a.s16 ? std::ldexp(1.0, -30) : 1.0 / (255.0 * 255.0), -2 * p.sexp);
+  a.sp = b->d_sp;
+  if ((rc = launch_bscan(a, h->sA)) != FMX_OK) {
+    h->err = "fmx_wb_bank_scan_process: kernel launch failed";
     return rc;
   }
   return FMX_OK;

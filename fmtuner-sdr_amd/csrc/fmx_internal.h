@@ -546,6 +546,30 @@ int launch_wbb_iqc_estimate(const WbbArgs &a, const WbbIqcArgs &q, void *stream)
 // launch_wbb with k_bank_iqc in k_wbb's place
 int launch_wbb_iqc(const WbbArgs &a, const WbbIqcArgs &q, void *stream);
 
+// ---- band scan over a capture bank (fmx_wb_bank_scan.inc) ----
+#define FMX_BSCAN_POINTS_MAX 8192 // the single scan's limit, over all captures
+struct BscanArgs {
+  const void *in;          // [S][wide_stride] wide samples, interleaved I/Q; n_out * D of each row are read
+  size_t wide_stride;      // samples
+  int s16, in_al;          // as WbArgs
+  int D, tpp, Lp, n_out, P, S; // P: the points of all captures
+  const uint16_t *w;       // [P][4][Lp] weight rows
+  const int *groups;       // [G][3] capture, first point, points (1..64): fmx_wb_bank_scan_groups
+  int G;
+  const int *pt_slot;      // [P] 16 (4 entry + wave) + column: where the point's partials lie
+  const int *pt_cap;       // [P] the capture a point belongs to
+  float *partial;          // [4 G][nwg][16] sums of |raw y|^2
+  uint32_t *clip;          // [S][nclip][2] (k_wbb_clip's)
+  float *sm;               // [P][2] smoother value, initialised flag
+  fmx_signal_level *level; // [P]
+  double pscale;           // raw |y|^2 -> |y|^2
+  const double *sp;        // [S][4] gain*factor, bias, floor, ceil of each capture (device)
+  int nt, nwg, nclip;      // as WbScanArgs (set by the launcher)
+};
+// the work list of k_bscan (fmx_wb_design.cpp; fmx_wb_bank_scan_groups is its C entry)
+int bscan_groups(const int *first_point, int n_captures, int *out, int cap);
+int launch_bscan(const BscanArgs &a, void *stream); // k_wbb_clip, k_bscan, k_bscan_level
+
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps
 

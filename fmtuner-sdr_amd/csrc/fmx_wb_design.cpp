@@ -279,7 +279,36 @@ int wbb_groups(const int *first_channel, int n_captures, int *out, int cap) {
   return g;
 }
 
+// The bank scan's work list (k_bscan): one entry
+// {capture, first point, points 1..64} per 64 points of a capture (a workgroup's
+// four waves of 16), in point order, none for an empty capture.  Returns and
+// errors as wbb_groups.
+int bscan_groups(const int *first_point, int n_captures, int *out, int cap) {
+  if (!first_point || n_captures < 1 || n_captures > FMX_WBB_CAPTURES_MAX || first_point[0] != 0) return FMX_E_INVALID;
+  int64_t G = 0;
+  for (int s = 0; s < n_captures; ++s) {
+    const int64_t n = static_cast<int64_t>(first_point[s + 1]) - first_point[s];
+    if (n < 0) return FMX_E_INVALID;
+    G += (n + 63) / 64;
+  }
+  if (G > FMX_WBB_GROUPS_MAX) return FMX_E_CAPACITY;
+  if (G > 0 && (!out || cap < G)) return -static_cast<int>(G);
+  int g = 0;
+  for (int s = 0; s < n_captures; ++s)
+    for (int64_t c = first_point[s]; c < first_point[s + 1]; c += 64) {
+      out[3 * g] = s;
+      out[3 * g + 1] = static_cast<int>(c);
+      out[3 * g + 2] = static_cast<int>(std::min<int64_t>(64, first_point[s + 1] - c));
+      ++g;
+    }
+  return g;
+}
+
 } // namespace fmx
+
+extern "C" int fmx_wb_bank_scan_groups(const int *first_point, int n_captures, int *out, int cap) {
+  return fmx::bscan_groups(first_point, n_captures, out, cap);
+}
 
 extern "C" int fmx_wb_bank_groups(const int *first_channel, int n_captures, int *out, int cap) {
   return fmx::wbb_groups(first_channel, n_captures, out, cap);

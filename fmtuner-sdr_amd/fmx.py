@@ -153,6 +153,12 @@ def lib():
         "fmx_wb_scan_process": (i, [vp, vp, i, vp]),
         "fmx_wb_scan_points": (i, [C.POINTER(WbScanConfig), C.POINTER(i), i]),
         "fmx_scan_peaks": (i, [C.POINTER(C.c_double), i, C.c_double, i, C.POINTER(i), i]),
+        "fmx_wb_bank_scan_create": (i, [vp, C.POINTER(WbConfig), i, C.POINTER(i), C.POINTER(i), C.POINTER(vp)]),
+        "fmx_wb_bank_scan_destroy": (i, [vp]),
+        "fmx_wb_bank_scan_set_signal_params": (i, [vp, i, i, C.c_double, C.c_double, C.c_double, C.c_double]),
+        "fmx_wb_bank_scan_reset": (i, [vp, i]),
+        "fmx_wb_bank_scan_process": (i, [vp, vp, C.c_size_t, i, vp]),
+        "fmx_wb_bank_scan_groups": (i, [C.POINTER(i), i, C.POINTER(i), i]),
         "fmx_wb_set_iq_correction": (i, [vp, i, C.POINTER(IqCorrection), C.c_double]),
         "fmx_wb_iq_correction": (i, [vp, C.POINTER(IqCorrection)]),
         "fmx_wb_scan_set_iq_correction": (i, [vp, i, C.POINTER(IqCorrection), C.c_double]),
@@ -667,6 +673,78 @@ class WidebandScan:
         out = IqCorrection()
         self._ck(self.L.fmx_wb_scan_iq_correction(self.s, C.byref(out)), "fmx_wb_scan_iq_correction")
         return out.astuple()
+
+
+class WidebandBankScan:
+    """The band scan over a capture bank (fmx_wb_bank_scan_*):
+    len(freqs_per_capture) wide captures of one plan, capture s with the scan
+    points freqs_per_capture[s] (a list, possibly empty, Hz from that
+    capture's centre), all read by one call.  The records are the captures'
+    in order: capture s owns [first_point[s], first_point[s + 1]).  Close it
+    before its handle."""
+
+    def __init__(self, handle, wcfg, freqs_per_capture):
+        self.L = lib()
+        self.handle = handle
+        self.cfg = wcfg
+        self.captures = len(freqs_per_capture)
+        self.first_point = [0]
+        for f in freqs_per_capture:
+            self.first_point.append(self.first_point[-1] + len(f))
+        self.n_points = self.first_point[-1]
+        flat = [int(v) for f in freqs_per_capture for v in f]
+        first = (C.c_int * (self.captures + 1))(*self.first_point)
+        f = (C.c_int * max(self.n_points, 1))(*flat)
+        b = C.c_void_p()
+        rc = self.L.fmx_wb_bank_scan_create(handle.h, C.byref(wcfg), self.captures, first, f, C.byref(b))
+        self.b = b if rc == FMX_OK else None
+        if rc != FMX_OK:
+            raise FmxError(f"fmx_wb_bank_scan_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+
+    def _ck(self, rc, what):
+        if rc != FMX_OK:
+            raise FmxError(f"{what} failed ({rc}): {self.L.fmx_last_error(self.handle.h).decode()}")
+
+    def close(self):
+        if self.b is not None and self.handle.h is not None:
+            self.L.fmx_wb_bank_scan_destroy(self.b)
+        self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process(self, d_wide, wide_stride, n_out, d_level):
+        """d_wide: [captures][wide_stride] interleaved I/Q samples, n_out * D
+        of each row read; d_level: [n_points] fmx_signal_level (40 bytes each)."""
+        self._ck(self.L.fmx_wb_bank_scan_process(self.b, C.c_void_p(d_wide), wide_stride, n_out, C.c_void_p(d_level)),
+                 "fmx_wb_bank_scan_process")
+
+    def set_signal_params(self, capture=-1, applied_gain_db=0, gain_comp_factor=0.5, bias_db=-4.0, floor_dbfs=-55.0,
+                          ceil_dbfs=-19.0):
+        self._ck(self.L.fmx_wb_bank_scan_set_signal_params(self.b, capture, applied_gain_db, gain_comp_factor,
+                                                           bias_db, floor_dbfs, ceil_dbfs),
+                 "fmx_wb_bank_scan_set_signal_params")
+
+    def reset(self, capture=-1):
+        """Clears the level smoothers of one capture's points (-1: all)."""
+        self._ck(self.L.fmx_wb_bank_scan_reset(self.b, capture), "fmx_wb_bank_scan_reset")
+
+
+def wb_bank_scan_groups(first_point):
+    """fmx_wb_bank_scan_groups: the bank scan kernel's work list as [(capture,
+    first point, points)] for a first_point table of captures + 1 entries."""
+    first = [int(v) for v in first_point]
+    n = len(first) - 1
+    cap = max(n, 0) + (max(first[-1], 0) // 64 if first else 0) + 1
+    t = (C.c_int * max(len(first), 1))(*first)
+    out = (C.c_int * (3 * cap))()
+    g = lib().fmx_wb_bank_scan_groups(t, n, out, cap)
+    if g < 0:
+        raise FmxError(f"fmx_wb_bank_scan_groups failed ({g})")
+    return [tuple(out[3 * k:3 * k + 3]) for k in range(g)]
 
 
 def wb_scan_points(scfg):

@@ -47,7 +47,10 @@
 extern "C" {
 #endif
 
-/* ABI history: the capture bank at rational rates (fmx_wb_bank_create_rational: many 2.048, 10 or 20 MS/s captures
+/* ABI history: the band scan over a capture bank (fmx_wb_bank_scan_create, fmx_wb_bank_scan_destroy,
+ * fmx_wb_bank_scan_set_signal_params, fmx_wb_bank_scan_reset, fmx_wb_bank_scan_process, fmx_wb_bank_scan_groups:
+ * every capture's scan points read in one call) arrived at 13 without a bump: additions only;
+ * the capture bank at rational rates (fmx_wb_bank_create_rational: many 2.048, 10 or 20 MS/s captures
  * channelized at P / Q in one call) arrived at 13 without a bump, as the bank and the rational rates did: an addition only;
  * the bank's correction per capture (fmx_wb_bank_set_iq_correction, fmx_wb_bank_iq_correction) arrived at 13
  * without a bump: additions only; the DC / IQ-imbalance correction (fmx_wb_set_iq_correction, fmx_wb_iq_correction,
@@ -512,6 +515,75 @@ int fmx_wb_scan_points(const fmx_wb_scan_config *cfg, int *freq_hz, int cap);
  * (a tie goes to the lowest index).  Writes the first min(cap, count) indices,
  * ascending; returns the count (negative on error). */
 int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int min_spacing, int *idx, int cap);
+
+/* ---- band scan over a capture bank: every capture's scan points in one call ----
+ * The scan for the bank's rig (sixteen dongles that together see the band):
+ * one call takes d_wide[n_captures][wide_stride] and writes one
+ * fmx_signal_level per scan point of every capture; fmx_scan_peaks over a
+ * capture's slice of the records gives the frequencies fmx_wb_bank_create
+ * takes.
+ * Plan and tables: cfg is the scan's plan, as fmx_wb_scan_config.wb is, and
+ * the accepted configurations are the same: dsp_rate is the points'
+ * measurement rate and need not be the handle's, wide_rate is an integer
+ * multiple D of it, 2 <= D <= 128, taps_per_phase and block mean what they
+ * mean in fmx_wb_scan_create and block must exceed taps_per_phase.  Capture s
+ * owns the points [first_point[s], first_point[s + 1]): first_point[0] is 0,
+ * the table does not decrease, an empty capture is legal; 1 <= n_captures <=
+ * 1024 and 1 <= first_point[n_captures] <= 8192.  freq_hz[p] is relative to
+ * the centre of the point's own capture and lies within +- wide_rate / 2.  The
+ * list is free-form, not a start / step grid: dongle centres rarely sit on the
+ * station grid.
+ * Equivalence: capture s behaves as an fmx_wb_scan object with the same
+ * fmx_wb_config and the same frequencies, fed row s of d_wide.  Where its
+ * frequencies form a start / step grid its records are bit for bit that
+ * object's -- dbfs, compensated_dbfs, level120, level120_smoothed and both clip
+ * ratios; where they do not, each record is bit for bit that of a one-point
+ * scan object at that frequency (a point's sum order is fixed by D, the padded
+ * filter length, the format and n_out alone).
+ * A call is one read of every point of every capture.  It consumes n_out * D
+ * samples of each row: wide_stride >= n_out * D, else FMX_E_INVALID; samples
+ * of a row past n_out * D are never read and nothing of the signal is kept
+ * between calls.  The outputs n < tpp are left out, as in the single scan;
+ * n_out <= tpp is FMX_E_INVALID, n_out > block FMX_E_CAPACITY.
+ * The clip ratios of a record are those of its capture's own n_out * D raw
+ * samples.  The signal parameters are per capture (every tuner has its own
+ * gain; -1: every capture's) and default to fmx_set_signal_params'; a set is
+ * ordered on the stage stream and holds for the process calls queued after it.
+ * fmx_wb_bank_scan_reset clears the level smoothers of the capture's points
+ * (-1: all), ordered behind the calls queued so far; the other captures'
+ * smoothers are untouched.
+ * Geometry: the d_wide base needs its element's alignment only (an unaligned
+ * base takes element loads and gives identical records), d_level 8 bytes;
+ * cells outside [0, first_point[n_captures]) are never written.  Calls are
+ * queued on the handle's stream exactly as fmx_wb_scan_process queues them,
+ * nothing synchronises with the host, and the object is destroyed before its
+ * handle.  One MFMA launch reads every point.
+ * The object is a kind of its own: every fmx_wb_bank_scan_* call handed an
+ * fmx_wb, bank or scan object returns FMX_E_INVALID with a message naming the
+ * function, the six IQ-correction calls (fmx_wb_set_iq_correction,
+ * fmx_wb_iq_correction, their _scan_ and their _bank_ forms) refuse a bank scan
+ * the same way, and every call with a NULL object returns FMX_E_INVALID
+ * without touching a device.
+ * Out of scope: IQ correction on a bank scan (k_wb_scan_iqc's epilogue and the
+ * bank's per-capture estimator would drop in: a follow-up); rational rates,
+ * for the single scan's reason (the scan's dsp_rate is free, so 2.048 MS/s
+ * scans at D = 8 or 16); mixed rates or formats within one object.
+ * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
+int fmx_wb_bank_scan_create(void *handle, const fmx_wb_config *cfg, int n_captures,
+                            const int *first_point /* [n_captures + 1] */,
+                            const int *freq_hz /* [first_point[n_captures]] */, void **bscan);
+int fmx_wb_bank_scan_destroy(void *bscan);
+int fmx_wb_bank_scan_set_signal_params(void *bscan, int capture /* -1: all */, int applied_gain_db,
+                                       double gain_comp_factor, double bias_db, double floor_dbfs, double ceil_dbfs);
+int fmx_wb_bank_scan_reset(void *bscan, int capture /* -1: all */);
+int fmx_wb_bank_scan_process(void *bscan, const void *d_wide, size_t wide_stride /* samples */, int n_out,
+                             fmx_signal_level *d_level /* [first_point[n_captures]] */);
+/* host only, no GPU: the scan kernel's work list, one entry {capture, first
+ * point, points 1..64} per 64 points of a capture and none for an empty
+ * capture, as out[G][3].  cap counts entries.  Returns and errors as
+ * fmx_wb_bank_groups: G; FMX_E_INVALID for a bad table or n_captures outside
+ * 1..1024; -G, with nothing written, when cap < G or out is NULL. */
+int fmx_wb_bank_scan_groups(const int *first_point, int n_captures, int *out /* [G][3] */, int cap);
 
 /* ---- DC offset and IQ imbalance of a wide capture ----
  * A zero-IF front end adds a DC offset (a carrier at the capture's centre)

@@ -2540,7 +2540,7 @@ int wbb_run(WbBank *b, const void *d_wide, size_t wide_stride, int n_out, float 
     rc = launch_wbb(a, h->sA);
   } else { // estimator, finisher, corrected channelizer: one launch each for every capture
     const WbbIqcArgs q{b->iqc.d_blk, b->d_iq_mode, b->iqc.d_partial, b->iqc.d_tsum};
-    if (b->iq_auto > 0) rc = launch_wbb_iqc_estimate(a, q, h->sA);
+    if (b->iq_auto > 0) rc = launch_wbb_iqc_estimate(a.in, a.wide_stride, static_cast<long>(a.n_out) * a.D, a.s16, a.S, q, h->sA);
     if (rc == FMX_OK) rc = launch_wbb_iqc(a, q, h->sA);
   }
   if (rc != FMX_OK) {
@@ -3113,6 +3113,13 @@ struct WbBankScan {
   uint32_t *d_clip = nullptr; // [S][clip workgroups of a full block][2]
   float *d_sm = nullptr;      // [P][2] level smoothers
   double *d_sp = nullptr;     // [S][4] signal parameters, written by k_wbb_set_params on sA
+  // fmx_wb_bank_scan_set_iq_correction, as WbBank keeps
+  // it: d_blk [S], d_partial [S][workgroups of a full block][5], d_tsum and
+  // tsum [P][2], allocated by the first set that leaves OFF
+  Iqc iqc;
+  WbbIqcMode *d_iq_mode = nullptr; // [S] mode and alpha, written with the blocks by k_bank_iqc_set on sA
+  std::vector<int> iq_mode;        // [S] the modes as of the reads queued so far: which kernels a read launches
+  int iq_on = 0, iq_auto = 0;      // captures out of OFF, captures in AUTO
 };
 void bscan_free(WbBankScan *b) {
   if (b->d_w) hipFree(b->d_w);
@@ -3123,6 +3130,8 @@ void bscan_free(WbBankScan *b) {
   if (b->d_clip) hipFree(b->d_clip);
   if (b->d_sm) hipFree(b->d_sm);
   if (b->d_sp) hipFree(b->d_sp);
+  if (b->d_iq_mode) hipFree(b->d_iq_mode);
+  iqc_free(b->iqc);
   delete b;
 }
 // the object behind an fmx_wb_bank_scan_* call, or NULL (with the handle's message set when there is an object)
@@ -3197,6 +3206,10 @@ int fmx_wb_bank_scan_create(void *handle, const fmx_wb_config *cfg, int n_captur
   const size_t row = static_cast<size_t>(4) * p.Lp;
   std::vector<uint16_t> rows(row * Pn);
   for (int k = 0; k < Pn; ++k) wb_weight_rows(p, freq_hz[k], rows.data() + row * k);
+  // the points' tap sums; a scan's frequencies are fixed, so nothing restages them
+  b->iqc.tsum.resize(static_cast<size_t>(2) * Pn);
+  for (int k = 0; k < Pn; ++k) wb_tap_sums(p, rows.data() + row * k, b->iqc.tsum.data() + 2 * k);
+  b->iq_mode.assign(n_captures, FMX_IQC_OFF);
   // where a point's partials lie and whose clip counts and parameters it takes
   std::vector<int> pt_slot(Pn), pt_cap(Pn);
   for (int e = 0; e < G; ++e)
@@ -3337,7 +3350,13 @@ int fmx_wb_bank_scan_process(void *bscan, const void *d_wide, size_t wide_stride
   // raw integers (2 b - 255 for u8) times weights * 2^sexp, squared
   a.pscale = std::ldexp(a.s16 ? std::ldexp(1.0, -30) : 1.0 / (255.0 * 255.0), -2 * p.sexp);
   a.sp = b->d_sp;
-  if ((rc = launch_bscan(a, h->sA)) != FMX_OK) {
+  if (b->iq_on == 0) {
+    rc = launch_bscan(a, h->sA);
+  } else { // estimator, finisher, corrected scan: one launch each for every capture
+    const WbbIqcArgs q{b->iqc.d_blk, b->d_iq_mode, b->iqc.d_partial, b->iqc.d_tsum};
+    rc = launch_bscan_iqc(a, q, b->iq_auto > 0, h->sA);
+  }
+  if (rc != FMX_OK) {
     h->err = "fmx_wb_bank_scan_process: kernel launch failed";
     return rc;
   }
@@ -3489,79 +3508,132 @@ WbBank *iqc_bank(void *bank, const char *who) {
 }
 } // namespace
 
-int fmx_wb_bank_set_iq_correction(void *bank, int capture, int mode, const fmx_iq_correction *fixed, double alpha) {
-  const char *who = "fmx_wb_bank_set_iq_correction";
-  WbBank *b = iqc_bank(bank, who);
-  if (!b) return FMX_E_INVALID;
-  Handle *h = b->h;
-  const char *bad = capture < -1 || capture >= b->S ? "capture out of range" : iqc_refused(mode, fixed, alpha);
+namespace {
+// The per-capture correction state of a bank or a bank scan: Iqc's buffers
+// with a capture dimension (d_blk [S], d_partial [S][workgroups of a full
+// block][5], d_tsum [channels or points][2]), the device's {mode, alpha} table
+// and the host's mirror of the modes.
+struct CapIqc {
+  Iqc &q;
+  WbbIqcMode *&d_mode;
+  std::vector<int> &mode;
+  int &on, &autos;
+};
+// capture's correction (-1: every capture's): validates, allocates on the
+// first mode other than OFF, queues k_bank_iqc_set on sA
+int cap_iqc_set(Handle *h, CapIqc c, int S, const WbPlan &p, const char *who, int capture, int mode,
+                const fmx_iq_correction *fixed, double alpha) {
+  const char *bad = capture < -1 || capture >= S ? "capture out of range" : iqc_refused(mode, fixed, alpha);
   if (bad) {
     h->err = std::string(who) + ": " + bad;
     return FMX_E_INVALID;
   }
-  Iqc &q = b->iqc;
+  Iqc &q = c.q;
   if (!q.d_blk && mode == FMX_IQC_OFF) return FMX_OK; // every capture is in OFF, and nothing exists yet
-  const WbPlan &p = b->p;
   const int s16 = p.format == FMX_WB_S16;
   HIP_TRY(hipSetDevice(h->device));
   if (!q.d_blk) {
-    const size_t nS = static_cast<size_t>(b->S);
+    const size_t nS = static_cast<size_t>(S);
     const size_t n_partial = nS * static_cast<size_t>(iqc_workgroups(static_cast<long>(p.block) * p.D, s16)) * 5;
     std::vector<FmxIqcBlock> blk(nS, iqc_block(FMX_IQC_OFF, nullptr, s16));
     std::vector<WbbIqcMode> tab(nS, WbbIqcMode{1.0 / 16.0, FMX_IQC_OFF, 0});
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&q.d_blk), nS * sizeof(FmxIqcBlock));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_iq_mode), nS * sizeof(WbbIqcMode));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c.d_mode), nS * sizeof(WbbIqcMode));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&q.d_partial), n_partial * sizeof(long long));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&q.d_tsum), q.tsum.size() * sizeof(float));
     // synchronous: the tables are complete before a corrected call is queued
     // (k_bank_iqc_set and fmx_wb_bank_set_freq keep them current from here on)
     if (e == hipSuccess) e = hipMemcpy(q.d_blk, blk.data(), nS * sizeof(FmxIqcBlock), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b->d_iq_mode, tab.data(), nS * sizeof(WbbIqcMode), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c.d_mode, tab.data(), nS * sizeof(WbbIqcMode), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(q.d_tsum, q.tsum.data(), q.tsum.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       iqc_free(q);
-      if (b->d_iq_mode) hipFree(b->d_iq_mode);
-      b->d_iq_mode = nullptr;
+      if (c.d_mode) hipFree(c.d_mode);
+      c.d_mode = nullptr;
       h->err = std::string(who) + ": " + hipGetErrorString(e);
       return FMX_E_NOMEM;
     }
   }
   // a one-thread kernel on sA: behind the calls queued so far, ahead of later ones
-  const WbbIqcArgs qa{q.d_blk, b->d_iq_mode, q.d_partial, q.d_tsum};
+  const WbbIqcArgs qa{q.d_blk, c.d_mode, q.d_partial, q.d_tsum};
   int rc;
-  if ((rc = launch_wbb_iqc_set(qa, b->S, capture, iqc_block(mode, fixed, s16), mode, alpha == 0.0 ? 1.0 / 16.0 : alpha,
+  if ((rc = launch_wbb_iqc_set(qa, S, capture, iqc_block(mode, fixed, s16), mode, alpha == 0.0 ? 1.0 / 16.0 : alpha,
                                h->sA)) != FMX_OK) {
     h->err = std::string(who) + ": kernel launch failed";
     return rc;
   }
-  for (int s = capture < 0 ? 0 : capture; s < (capture < 0 ? b->S : capture + 1); ++s) b->iq_mode[s] = mode;
-  b->iq_on = b->iq_auto = 0;
-  for (int m : b->iq_mode) {
-    b->iq_on += m != FMX_IQC_OFF;
-    b->iq_auto += m == FMX_IQC_AUTO;
+  for (int s = capture < 0 ? 0 : capture; s < (capture < 0 ? S : capture + 1); ++s) c.mode[s] = mode;
+  c.on = c.autos = 0;
+  for (int m : c.mode) {
+    c.on += m != FMX_IQC_OFF;
+    c.autos += m == FMX_IQC_AUTO;
   }
   return FMX_OK;
+}
+// capture's parameters as of the last call, behind the calls queued on sA
+int cap_iqc_get(Handle *h, CapIqc c, int S, const char *who, int capture, fmx_iq_correction *h_out) {
+  if (capture < 0 || capture >= S || !h_out) {
+    h->err = std::string(who) + (h_out ? ": capture out of range (one capture per call)" : ": null h_out");
+    return FMX_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->sA));
+  if (c.mode[capture] == FMX_IQC_OFF) {
+    *h_out = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
+    return FMX_OK;
+  }
+  FmxIqcBlock v;
+  HIP_TRY(hipMemcpy(&v, c.q.d_blk + capture, sizeof(v), hipMemcpyDeviceToHost));
+  *h_out = v.x;
+  return FMX_OK;
+}
+} // namespace
+
+int fmx_wb_bank_set_iq_correction(void *bank, int capture, int mode, const fmx_iq_correction *fixed, double alpha) {
+  const char *who = "fmx_wb_bank_set_iq_correction";
+  WbBank *b = iqc_bank(bank, who);
+  if (!b) return FMX_E_INVALID;
+  return cap_iqc_set(b->h, CapIqc{b->iqc, b->d_iq_mode, b->iq_mode, b->iq_on, b->iq_auto}, b->S, b->p, who, capture, mode,
+                     fixed, alpha);
 }
 
 int fmx_wb_bank_iq_correction(void *bank, int capture, fmx_iq_correction *h_out) {
   const char *who = "fmx_wb_bank_iq_correction";
   WbBank *b = iqc_bank(bank, who);
   if (!b) return FMX_E_INVALID;
-  Handle *h = b->h;
-  if (capture < 0 || capture >= b->S || !h_out) {
-    h->err = std::string(who) + (h_out ? ": capture out of range (one capture per call)" : ": null h_out");
-    return FMX_E_INVALID;
+  return cap_iqc_get(b->h, CapIqc{b->iqc, b->d_iq_mode, b->iq_mode, b->iq_on, b->iq_auto}, b->S, who, capture, h_out);
+}
+
+/* ---- the bank scan's correction, per capture (fmx.h; kernels in fmx_wb_bank_scan_iqc.inc) ---- */
+namespace {
+WbBankScan *iqc_bscan(void *bscan, const char *who) {
+  WbBankScan *b = static_cast<WbBankScan *>(bscan);
+  if (!b) return nullptr;
+  if (b->kind != WB_KIND_BSCAN) {
+    const char *takes = b->kind == WB_KIND_BANK   ? "a capture bank takes fmx_wb_bank_set_iq_correction / fmx_wb_bank_iq_correction"
+                        : b->kind == WB_KIND_SCAN ? "an fmx_wb_scan object takes fmx_wb_scan_set_iq_correction / fmx_wb_scan_iq_correction"
+                        : b->kind == WB_KIND_WB   ? "an fmx_wb object takes fmx_wb_set_iq_correction / fmx_wb_iq_correction"
+                                                  : "not an fmx_wb_bank_scan object";
+    b->h->err = std::string(who) + ": " + takes;
+    return nullptr;
   }
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->sA));
-  if (b->iq_mode[capture] == FMX_IQC_OFF) {
-    *h_out = fmx_iq_correction{0.0, 0.0, 1.0, 0.0};
-    return FMX_OK;
-  }
-  FmxIqcBlock v;
-  HIP_TRY(hipMemcpy(&v, b->iqc.d_blk + capture, sizeof(v), hipMemcpyDeviceToHost));
-  *h_out = v.x;
-  return FMX_OK;
+  return b;
+}
+} // namespace
+
+int fmx_wb_bank_scan_set_iq_correction(void *bscan, int capture, int mode, const fmx_iq_correction *fixed, double alpha) {
+  const char *who = "fmx_wb_bank_scan_set_iq_correction";
+  WbBankScan *b = iqc_bscan(bscan, who);
+  if (!b) return FMX_E_INVALID;
+  return cap_iqc_set(b->h, CapIqc{b->iqc, b->d_iq_mode, b->iq_mode, b->iq_on, b->iq_auto}, b->S, b->p, who, capture, mode,
+                     fixed, alpha);
+}
+
+int fmx_wb_bank_scan_iq_correction(void *bscan, int capture, fmx_iq_correction *h_out) {
+  const char *who = "fmx_wb_bank_scan_iq_correction";
+  WbBankScan *b = iqc_bscan(bscan, who);
+  if (!b) return FMX_E_INVALID;
+  return cap_iqc_get(b->h, CapIqc{b->iqc, b->d_iq_mode, b->iq_mode, b->iq_on, b->iq_auto}, b->S, who, capture, h_out);
 }
 
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes) {

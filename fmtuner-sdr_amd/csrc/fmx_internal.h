@@ -541,8 +541,9 @@ struct WbbIqcArgs {
 };
 // capture's block, mode and alpha (-1: every capture's) on the stream
 int launch_wbb_iqc_set(const WbbIqcArgs &q, int S, int capture, const FmxIqcBlock &v, int mode, double alpha, void *stream);
-// the estimator and the finisher over row s of the call's input for every capture in AUTO
-int launch_wbb_iqc_estimate(const WbbArgs &a, const WbbIqcArgs &q, void *stream);
+// the estimator and the finisher over the first n_in raw samples of row s of
+// [S][wide_stride] for every capture in AUTO (the bank's call, the bank scan's read)
+int launch_wbb_iqc_estimate(const void *in, size_t wide_stride, long n_in, int s16, int S, const WbbIqcArgs &q, void *stream);
 // launch_wbb with k_bank_iqc in k_wbb's place
 int launch_wbb_iqc(const WbbArgs &a, const WbbIqcArgs &q, void *stream);
 
@@ -569,6 +570,10 @@ struct BscanArgs {
 // the work list of k_bscan (fmx_wb_design.cpp; fmx_wb_bank_scan_groups is its C entry)
 int bscan_groups(const int *first_point, int n_captures, int *out, int cap);
 int launch_bscan(const BscanArgs &a, void *stream); // k_wbb_clip, k_bscan, k_bscan_level
+// a read with a capture out of OFF (fmx_wb_bank_scan_iqc.inc):
+// the bank's estimator (any_auto), k_wbb_clip, k_scan_bank_iqc, k_bscan_level;
+// q.tsum: [P][2] tap sums of the points
+int launch_bscan_iqc(const BscanArgs &a, const WbbIqcArgs &q, int any_auto, void *stream);
 
 int launch_iq_to_u8(const float *in, int in_stride, int C, int n, uint8_t *out, size_t out_stride, void *stream);
 int launch_copy16(const void *src, void *dst, size_t n16, void *stream); // 16-B words, any memory the device maps

@@ -3960,5 +3960,6 @@ int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sa
 #include "fmx_wb_iqc.inc"
 #include "fmx_wb_bank_iqc.inc"
 #include "fmx_wb_bank_scan.inc"
+#include "fmx_wb_bank_scan_iqc.inc"
 #include "fmx_fecf.inc"
 } // namespace fmx

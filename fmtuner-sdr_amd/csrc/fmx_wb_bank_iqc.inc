@@ -108,19 +108,18 @@ int launch_wbb_iqc_set(const WbbIqcArgs &q, int S, int capture, const FmxIqcBloc
   return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
 }
 
-int launch_wbb_iqc_estimate(const WbbArgs &a, const WbbIqcArgs &q, void *stream) {
-  const long n_in = (long)a.n_out * a.D;
-  if (!a.in || !q.blk || !q.mode || !q.partial || a.S < 1 || a.S > FMX_WBB_CAPTURES_MAX || n_in < 1 ||
-      a.wide_stride < (size_t)n_in)
+// the first n_in raw samples of rows [S][wide_stride]: the bank's call and the bank scan's read
+int launch_wbb_iqc_estimate(const void *in, size_t wide_stride, long n_in, int s16, int S, const WbbIqcArgs &q, void *stream) {
+  if (!in || !q.blk || !q.mode || !q.partial || S < 1 || S > FMX_WBB_CAPTURES_MAX || n_in < 1 || wide_stride < (size_t)n_in)
     return FMX_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nwg = iqc_workgroups(n_in, a.s16);
-  const dim3 grid((unsigned)nwg, (unsigned)a.S);
-  if (a.s16) hipLaunchKernelGGL(k_bank_iqc_sums<int16_t>, grid, dim3(256), 0, st, a.in, a.wide_stride, n_in, q.mode, q.partial);
-  else hipLaunchKernelGGL(k_bank_iqc_sums<uint8_t>, grid, dim3(256), 0, st, a.in, a.wide_stride, n_in, q.mode, q.partial);
+  const int nwg = iqc_workgroups(n_in, s16);
+  const dim3 grid((unsigned)nwg, (unsigned)S);
+  if (s16) hipLaunchKernelGGL(k_bank_iqc_sums<int16_t>, grid, dim3(256), 0, st, in, wide_stride, n_in, q.mode, q.partial);
+  else hipLaunchKernelGGL(k_bank_iqc_sums<uint8_t>, grid, dim3(256), 0, st, in, wide_stride, n_in, q.mode, q.partial);
   if (hipGetLastError() != hipSuccess) return FMX_E_HIP;
-  hipLaunchKernelGGL(k_bank_iqc_finish, dim3((unsigned)((a.S + 63) / 64)), dim3(64), 0, st, q.partial, nwg, n_in,
-                     a.s16 ? 32768.0 : 255.0, q.mode, q.blk, a.S);
+  hipLaunchKernelGGL(k_bank_iqc_finish, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, q.partial, nwg, n_in,
+                     s16 ? 32768.0 : 255.0, q.mode, q.blk, S);
   return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
 }
 

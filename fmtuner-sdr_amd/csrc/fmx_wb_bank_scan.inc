@@ -71,9 +71,10 @@ __global__ __launch_bounds__(64) void k_bscan_level(BscanArgs a) {
                                (double)((long)a.n_out * a.D), a.sp + 4 * (size_t)cap, a.sm + 2 * (size_t)p);
 }
 
-// k_wbb_clip over the n_out D raw samples of every row, k_bscan over
-// (workgroups of the call) x (entries), k_bscan_level over the points
-int launch_bscan(const BscanArgs &a0, void *stream) {
+// k_wbb_clip over the n_out D raw samples of every row, the scan kernel
+// (k_bscan, or fmx_wb_bank_scan_iqc.inc's) over (workgroups of the call) x
+// (entries), k_bscan_level over the points
+template <class Launch> static int bscan_run(const BscanArgs &a0, void *stream, Launch launch) {
   BscanArgs a = a0;
   if (a.P <= 0 || a.S <= 0 || a.S > FMX_WBB_CAPTURES_MAX || a.G <= 0 || a.G > FMX_WBB_GROUPS_MAX || a.D < 2 || a.tpp < 1 ||
       a.Lp < a.D * a.tpp || (a.Lp & 31) || a.n_out <= a.tpp || a.wide_stride < (size_t)a.n_out * (size_t)a.D)
@@ -98,8 +99,14 @@ int launch_bscan(const BscanArgs &a0, void *stream) {
   if (a.s16) hipLaunchKernelGGL(k_wbb_clip<int16_t>, cgrid, dim3(256), 0, st, c);
   else hipLaunchKernelGGL(k_wbb_clip<uint8_t>, cgrid, dim3(256), 0, st, c);
   if (hipGetLastError() != hipSuccess) return FMX_E_HIP;
-  const int rc = WB_LAUNCH(k_bscan, a.s16, (a.D & 1) == 0, dim3((unsigned)a.nwg, (unsigned)a.G), smem, st, a);
+  const int rc = launch(a, smem, dim3((unsigned)a.nwg, (unsigned)a.G), st);
   if (rc != FMX_OK) return rc;
   hipLaunchKernelGGL(k_bscan_level, dim3((unsigned)((a.P + 63) / 64)), dim3(64), 0, st, a);
   return hipGetLastError() == hipSuccess ? FMX_OK : FMX_E_HIP;
+}
+
+int launch_bscan(const BscanArgs &a0, void *stream) {
+  return bscan_run(a0, stream, [](const BscanArgs &a, size_t smem, dim3 grid, hipStream_t st) {
+    return WB_LAUNCH(k_bscan, a.s16, (a.D & 1) == 0, grid, smem, st, a);
+  });
 }

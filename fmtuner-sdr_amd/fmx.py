@@ -165,6 +165,8 @@ def lib():
         "fmx_wb_scan_iq_correction": (i, [vp, C.POINTER(IqCorrection)]),
         "fmx_wb_bank_set_iq_correction": (i, [vp, i, i, C.POINTER(IqCorrection), C.c_double]),
         "fmx_wb_bank_iq_correction": (i, [vp, i, C.POINTER(IqCorrection)]),
+        "fmx_wb_bank_scan_set_iq_correction": (i, [vp, i, i, C.POINTER(IqCorrection), C.c_double]),
+        "fmx_wb_bank_scan_iq_correction": (i, [vp, i, C.POINTER(IqCorrection)]),
         "fmx_iq_estimate": (i, [vp, i, C.c_long, C.POINTER(IqCorrection)]),
         "fmx_malloc": (i, [vp, C.POINTER(vp), sz]),
         "fmx_free": (i, [vp, vp]),
@@ -731,6 +733,20 @@ class WidebandBankScan:
     def reset(self, capture=-1):
         """Clears the level smoothers of one capture's points (-1: all)."""
         self._ck(self.L.fmx_wb_bank_scan_reset(self.b, capture), "fmx_wb_bank_scan_reset")
+
+    def set_iq_correction(self, mode, fixed=None, alpha=0.0, capture=-1):
+        """fmx_wb_bank_scan_set_iq_correction: WidebandScan.set_iq_correction
+        for one capture (-1: every capture), from the next read on."""
+        self._ck(self.L.fmx_wb_bank_scan_set_iq_correction(self.b, capture, mode, _iq_fixed(fixed), alpha),
+                 "fmx_wb_bank_scan_set_iq_correction")
+
+    def iq_correction(self, capture):
+        """fmx_wb_bank_scan_iq_correction: waits for the queued calls; the
+        capture's (dc_i, dc_q, gain, cross) as of the last read."""
+        out = IqCorrection()
+        self._ck(self.L.fmx_wb_bank_scan_iq_correction(self.b, capture, C.byref(out)),
+                 "fmx_wb_bank_scan_iq_correction")
+        return out.astuple()
 
 
 def wb_bank_scan_groups(first_point):

@@ -47,7 +47,9 @@
 extern "C" {
 #endif
 
-/* ABI history: the band scan over a capture bank (fmx_wb_bank_scan_create, fmx_wb_bank_scan_destroy,
+/* ABI history: the bank scan's correction per capture (fmx_wb_bank_scan_set_iq_correction,
+ * fmx_wb_bank_scan_iq_correction) arrived at 13 without a bump: additions only;
+ * the band scan over a capture bank (fmx_wb_bank_scan_create, fmx_wb_bank_scan_destroy,
  * fmx_wb_bank_scan_set_signal_params, fmx_wb_bank_scan_reset, fmx_wb_bank_scan_process, fmx_wb_bank_scan_groups:
  * every capture's scan points read in one call) arrived at 13 without a bump: additions only;
  * the capture bank at rational rates (fmx_wb_bank_create_rational: many 2.048, 10 or 20 MS/s captures
@@ -564,9 +566,9 @@ int fmx_scan_peaks(const double *dbfs, int n, double min_dbfs, int min_spacing, 
  * fmx_wb_iq_correction, their _scan_ and their _bank_ forms) refuse a bank scan
  * the same way, and every call with a NULL object returns FMX_E_INVALID
  * without touching a device.
- * Out of scope: IQ correction on a bank scan (k_wb_scan_iqc's epilogue and the
- * bank's per-capture estimator would drop in: a follow-up); rational rates,
- * for the single scan's reason (the scan's dsp_rate is free, so 2.048 MS/s
+ * DC offset and IQ imbalance are corrected per capture by
+ * fmx_wb_bank_scan_set_iq_correction below.
+ * Out of scope: rational rates, for the single scan's reason (the scan's dsp_rate is free, so 2.048 MS/s
  * scans at D = 8 or 16); mixed rates or formats within one object.
  * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
 int fmx_wb_bank_scan_create(void *handle, const fmx_wb_config *cfg, int n_captures,
@@ -671,6 +673,40 @@ int fmx_iq_estimate(const void *h_raw, int format, long n_samples, fmx_iq_correc
 int fmx_wb_bank_set_iq_correction(void *bank, int capture, int mode, const fmx_iq_correction *fixed, double alpha);
 /* waits for the queued calls; capture's parameters as of the last one (identity in OFF) */
 int fmx_wb_bank_iq_correction(void *bank, int capture, fmx_iq_correction *h_out);
+
+/* ---- band scan over a capture bank: DC offset and IQ imbalance per capture ----
+ * An uncorrected scan of a zero-IF front end finds a ghost at 0 Hz and one
+ * image per strong station, and a bank that tunes itself from the scan spends
+ * channels on them; every dongle has its own DC and mismatch, so every capture
+ * of a bank scan has its own mode, parameters, alpha and smoothed moments.
+ * Capture s behaves as an fmx_wb_scan object with the same fmx_wb_config and
+ * frequencies, fed row s, that was given the same
+ * fmx_wb_scan_set_iq_correction calls at the same points of its stream: the
+ * records (all six fields) and the read-back agree bit for bit in every mode,
+ * a capture left in OFF beside corrected ones included; off a start / step
+ * grid each record is bit for bit a one-point scan object's at that frequency
+ * set the same way.  AUTO's sums run over the capture's own n_out * D raw
+ * samples of the read (the padding of a row is never read) and each read is
+ * otherwise independent: only the smoothed moments carry over.  The clip
+ * ratios stay those of the raw samples; an empty capture is legal in every
+ * mode, and in AUTO its read-back follows the estimator on its row.  The set
+ * is ordered on the stage stream behind the reads queued so far, holds from
+ * the next read on and restarts that capture's estimate;
+ * fmx_wb_bank_scan_reset and fmx_wb_bank_scan_set_signal_params leave the
+ * estimate alone.  A read costs at most five launches whatever the number of
+ * captures, with no host synchronisation; an object whose captures are all in
+ * OFF allocates nothing and launches what it launched before these calls
+ * existed.
+ * FMX_E_INVALID (message naming the function) for a capture outside
+ * [-1, n_captures), whatever fmx_wb_set_iq_correction refuses, a NULL h_out,
+ * capture -1 in the read-back and an object that is not a bank scan; a NULL
+ * object returns FMX_E_INVALID without touching a device.
+ * These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
+/* capture's correction (-1: every capture's) */
+int fmx_wb_bank_scan_set_iq_correction(void *bscan, int capture, int mode,
+                                       const fmx_iq_correction *fixed, double alpha);
+/* waits for the queued calls; capture's parameters as of the last read (identity in OFF) */
+int fmx_wb_bank_scan_iq_correction(void *bscan, int capture, fmx_iq_correction *h_out);
 
 /* ---- device memory helpers (so C/FFI callers need no HIP headers) ---- */
 int fmx_malloc(void *handle, void **d_ptr, size_t bytes);

@@ -17,6 +17,7 @@
 
 #include "fmx_internal.h"
 #include "fmx_synth.h"
+#include "fmx_synth_band.h"
 
 namespace fmx {
 
@@ -1922,10 +1923,23 @@ int fmx_rds(void *handle, const float *d_mpx, int mpx_stride, int n, fmx_rds_gro
 
 /* ---- wideband channelizer (fmx.h; design in fmx_wb_design.cpp, kernel in fmx_wb.inc) ---- */
 namespace {
-// The first two members of Wb, WbBank, WbScan and WbBankScan are alike, so
-// that a call handed the wrong kind of object (fmx_wb_set_iq_correction on a
-// bank) can tell and refuse.
-enum WbKind { WB_KIND_WB = 0x5742, WB_KIND_BANK = 0x5743, WB_KIND_SCAN = 0x5744, WB_KIND_BSCAN = 0x5745 };
+// The first two members of Wb, WbBank, WbScan, WbBankScan and SynthBand are
+// alike, so that a call handed the wrong kind of object
+// (fmx_wb_set_iq_correction on a bank) can tell and refuse.
+enum WbKind { WB_KIND_WB = 0x5742, WB_KIND_BANK = 0x5743, WB_KIND_SCAN = 0x5744, WB_KIND_BSCAN = 0x5745, WB_KIND_SBAND = 0x5746 };
+struct ObjHead {
+  Handle *h;
+  int kind;
+};
+// p unless it is a synthetic band (fmx_synth_band_create), which no channelizer, bank or scan call takes
+void *not_synth_band(void *p) {
+  ObjHead *o = static_cast<ObjHead *>(p);
+  if (o && o->kind == WB_KIND_SBAND) {
+    o->h->err = "a synthetic band object takes fmx_synth_band_generate / fmx_synth_band_destroy only";
+    return nullptr;
+  }
+  return p;
+}
 // DC / IQ-imbalance correction of one object (fmx.h; kernels in fmx_wb_iqc.inc,
 // DESIGN.md section 24).  Nothing is allocated or launched while the mode has
 // never left FMX_IQC_OFF.
@@ -1986,7 +2000,7 @@ struct Wb {
   float *d_sm = nullptr;      // [C][2] level smoothers
   double sp[4] = {0.0, -4.0, -55.0, -19.0}; // gain*factor, bias, floor, ceil
 };
-Wb *W(void *p) { return static_cast<Wb *>(p); }
+Wb *W(void *p) { return static_cast<Wb *>(not_synth_band(p)); }
 size_t wb_sample_bytes(const WbPlan &p) { return p.format == FMX_WB_S16 ? 4 : 2; }
 // wide samples a call of n outputs consumes (n a multiple of Q on a rational object)
 int64_t wb_consumed(const Wb *w, int n) {
@@ -2452,7 +2466,7 @@ struct WbBank {
   std::vector<int> iq_mode;        // [S] the modes as of the calls queued so far: which kernels a call launches
   int iq_on = 0, iq_auto = 0;      // captures out of OFF, captures in AUTO
 };
-WbBank *WBK(void *p) { return static_cast<WbBank *>(p); }
+WbBank *WBK(void *p) { return static_cast<WbBank *>(not_synth_band(p)); }
 // wide samples of every row a call of n outputs consumes (n a multiple of Q on a rational bank)
 int64_t wbb_consumed(const WbBank *b, int n) {
   return b->rational ? static_cast<int64_t>(n) / b->rp.Q * b->rp.P : static_cast<int64_t>(n) * b->p.D;
@@ -2952,7 +2966,7 @@ struct WbScan {
   float *d_sm = nullptr;      // [P][2] level smoothers
   double sp[4] = {0.0, -4.0, -55.0, -19.0}; // gain*factor, bias, floor, ceil
 };
-WbScan *WS(void *p) { return static_cast<WbScan *>(p); }
+WbScan *WS(void *p) { return static_cast<WbScan *>(not_synth_band(p)); }
 void wb_scan_free(WbScan *s) {
   if (s->d_w) hipFree(s->d_w);
   if (s->d_partial) hipFree(s->d_partial);
@@ -3358,6 +3372,149 @@ int fmx_wb_bank_scan_process(void *bscan, const void *d_wide, size_t wide_stride
   }
   if (rc != FMX_OK) {
     h->err = "fmx_wb_bank_scan_process: kernel launch failed";
+    return rc;
+  }
+  return FMX_OK;
+}
+
+/* ---- synthetic FM band (fmx.h; definition in fmx_synth_band.h, host loop in fmx_synth_band.cpp,
+ * kernel in fmx_synth_band.inc) ---- */
+namespace {
+struct SynthBand {
+  Handle *h = nullptr;
+  int kind = WB_KIND_SBAND;
+  fmx_synth_band_config cfg{};
+  int S = 0, G = 0;               // captures, stations of all captures
+  fmx_sb_station *d_st = nullptr; // [max(G, 1)] derived stations
+  int *d_first = nullptr;         // [S + 1]
+  uint8_t *d_bits = nullptr;      // [G][n_bits] (kind 2; one byte otherwise)
+  double *d_fe = nullptr;         // [S][4] dc_i, dc_q, q_gain, q_cross
+};
+void sband_free(SynthBand *b) {
+  if (b->d_st) hipFree(b->d_st);
+  if (b->d_first) hipFree(b->d_first);
+  if (b->d_bits) hipFree(b->d_bits);
+  if (b->d_fe) hipFree(b->d_fe);
+  delete b;
+}
+// the object behind an fmx_synth_band_* call, or NULL (with the handle's message set when there is an object)
+SynthBand *SBD(void *p, const char *who) {
+  SynthBand *b = static_cast<SynthBand *>(p);
+  if (!b) return nullptr;
+  if (b->kind != WB_KIND_SBAND) {
+    b->h->err = std::string(who) + ": not an fmx_synth_band object";
+    return nullptr;
+  }
+  return b;
+}
+} // namespace
+
+int fmx_synth_band_create(void *handle, const fmx_synth_band_config *cfg, uint32_t ch0, int n_captures,
+                          const int *first_station, const fmx_synth_station *stations,
+                          const fmx_synth_frontend *frontends, const uint8_t *h_bits, void **band) {
+  const char *who = "fmx_synth_band_create";
+  Handle *h = H(handle);
+  if (band) *band = nullptr;
+  if (!h) return FMX_E_INVALID;
+  if (!band) {
+    h->err = std::string(who) + ": null argument";
+    return FMX_E_INVALID;
+  }
+  int rc = synth_band_check(who, cfg, n_captures, first_station, stations, frontends, h_bits, &h->err);
+  if (rc != FMX_OK) return rc;
+  const int G = first_station[n_captures];
+  fmx_synth_config content;
+  synth_band_content(*cfg, &content);
+  std::vector<fmx_sb_station> st(static_cast<size_t>(std::max(G, 1)));
+  std::memset(st.data(), 0, st.size() * sizeof(fmx_sb_station));
+  for (int g = 0; g < G; ++g)
+    fmx_sb_derive(&content, ch0 + static_cast<uint32_t>(g), stations[g].freq_hz, stations[g].amplitude, &st[g]);
+  std::vector<double> fe(static_cast<size_t>(4) * n_captures);
+  for (int s = 0; s < n_captures; ++s) {
+    fe[4 * s] = frontends ? frontends[s].dc_i : 0.0;
+    fe[4 * s + 1] = frontends ? frontends[s].dc_q : 0.0;
+    fe[4 * s + 2] = frontends ? frontends[s].q_gain : 1.0;
+    fe[4 * s + 3] = frontends ? frontends[s].q_cross : 0.0;
+  }
+  const bool rds = cfg->kind == FMX_SYNTH_STEREO_RDS && G > 0;
+  const size_t bits_bytes = rds ? static_cast<size_t>(G) * static_cast<size_t>(cfg->n_bits) : 1;
+  HIP_TRY(hipSetDevice(h->device));
+  SynthBand *b = new (std::nothrow) SynthBand();
+  if (!b) return FMX_E_NOMEM;
+  b->h = h;
+  b->cfg = *cfg;
+  b->S = n_captures;
+  b->G = G;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_st), st.size() * sizeof(fmx_sb_station));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_first), (static_cast<size_t>(n_captures) + 1) * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_bits), bits_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_fe), fe.size() * sizeof(double));
+  if (e != hipSuccess) {
+    h->err = std::string(who) + ": hipMalloc failed: " + hipGetErrorString(e);
+    sband_free(b);
+    return FMX_E_NOMEM;
+  }
+  // synchronous: the tables are complete before the first call is queued
+  e = hipMemcpy(b->d_st, st.data(), st.size() * sizeof(fmx_sb_station), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->d_first, first_station, (static_cast<size_t>(n_captures) + 1) * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = rds ? hipMemcpy(b->d_bits, h_bits, bits_bytes, hipMemcpyHostToDevice) : hipMemset(b->d_bits, 0, bits_bytes);
+  if (e == hipSuccess) e = hipMemcpy(b->d_fe, fe.data(), fe.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    h->err = std::string(who) + ": " + hipGetErrorString(e);
+    sband_free(b);
+    return FMX_E_HIP;
+  }
+  *band = b;
+  return FMX_OK;
+}
+
+int fmx_synth_band_destroy(void *band) {
+  SynthBand *b = SBD(band, "fmx_synth_band_destroy");
+  if (!b) return FMX_E_INVALID;
+  if (b->h->sA) hipStreamSynchronize(b->h->sA);
+  sband_free(b);
+  return FMX_OK;
+}
+
+int fmx_synth_band_generate(void *band, int64_t sample0, int n_samples, void *d_out, size_t wide_stride) {
+  const char *who = "fmx_synth_band_generate";
+  SynthBand *b = SBD(band, who);
+  if (!b) return FMX_E_INVALID;
+  Handle *h = b->h;
+  int rc = synth_band_window(who, sample0, n_samples, wide_stride, &h->err);
+  if (rc != FMX_OK) return rc;
+  if (n_samples == 0) return FMX_OK;
+  const bool s16 = b->cfg.format == FMX_WB_S16;
+  if (!d_out) {
+    h->err = std::string(who) + ": null buffer";
+    return FMX_E_INVALID;
+  }
+  if (s16 && (reinterpret_cast<uintptr_t>(d_out) & 1)) {
+    h->err = std::string(who) + ": d_out is not 2-byte aligned";
+    return FMX_E_INVALID;
+  }
+  // on sA behind whatever the other stage streams have queued, as fmx_wb_process is
+  if ((rc = join_into_A(h)) != FMX_OK) return rc;
+  SbArgs a{};
+  a.out = d_out;
+  a.wide_stride = wide_stride;
+  a.n = n_samples;
+  a.sample0 = sample0;
+  a.st = b->d_st;
+  a.first = b->d_first;
+  a.bits = b->d_bits;
+  a.fe = b->d_fe;
+  a.S = b->S;
+  a.fs = b->cfg.wide_rate;
+  a.kind = b->cfg.kind;
+  a.n_bits = b->cfg.n_bits;
+  a.s16 = s16;
+  a.seed_base = b->cfg.seed_base;
+  a.noise_std = static_cast<double>(b->cfg.noise_std);
+  a.krds = fmx_sb_krds(b->cfg.rds_level);
+  if ((rc = launch_synth_band(a, h->sA)) != FMX_OK) {
+    h->err = std::string(who) + ": kernel launch failed";
     return rc;
   }
   return FMX_OK;

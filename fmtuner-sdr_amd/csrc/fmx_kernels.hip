@@ -34,6 +34,7 @@
 #include "fmx_internal.h"
 #include "fmx_math.h"
 #include "fmx_synth.h"
+#include "fmx_synth_band.h"
 
 // k_rds's FIR partial sums: one packed FMA per product instead of the
 // reference's separate multiply and add (its dotprod order, rounded twice).
@@ -3961,5 +3962,6 @@ int launch_synth(const fmx_synth_config &cfg, uint32_t ch0, int n_ch, int64_t sa
 #include "fmx_wb_bank_iqc.inc"
 #include "fmx_wb_bank_scan.inc"
 #include "fmx_wb_bank_scan_iqc.inc"
+#include "fmx_synth_band.inc"
 #include "fmx_fecf.inc"
 } // namespace fmx

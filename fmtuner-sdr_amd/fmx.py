@@ -67,6 +67,20 @@ class SynthConfig(C.Structure):
 FMX_WB_U8, FMX_WB_S16 = 0, 1
 
 
+class SynthBandConfig(C.Structure):
+    _fields_ = [("wide_rate", C.c_int), ("format", C.c_int), ("kind", C.c_int), ("seed_base", C.c_uint32),
+                ("max_offset_hz", C.c_int), ("rds_level", C.c_float), ("n_bits", C.c_int), ("noise_std", C.c_float)]
+
+
+class SynthStation(C.Structure):
+    _fields_ = [("freq_hz", C.c_int), ("amplitude", C.c_float)]
+
+
+class SynthFrontend(C.Structure):
+    """fmx_synth_frontend: I' = I + dc_i, Q' = q_gain Q + q_cross I + dc_q."""
+    _fields_ = [(n, C.c_double) for n in ("dc_i", "dc_q", "q_gain", "q_cross")]
+
+
 class WbConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("wide_rate", "dsp_rate", "format", "taps_per_phase", "block")]
 
@@ -181,6 +195,15 @@ def lib():
         "fmx_synth_rds_bits": (i, [C.POINTER(SynthConfig), C.c_uint32, i, vp, vp]),
         "fmx_synth_host": (i, [C.POINTER(SynthConfig), C.c_uint32, i, C.c_int64, i, vp, vp, sz, i]),
         "fmx_synth_device": (i, [vp, C.POINTER(SynthConfig), C.c_uint32, i, C.c_int64, i, vp, vp, sz]),
+        "fmx_synth_band_content": (i, [C.POINTER(SynthBandConfig), C.POINTER(SynthConfig)]),
+        "fmx_synth_band_tile": (i, []),
+        "fmx_synth_band_error": (C.c_char_p, []),
+        "fmx_synth_band_host": (i, [C.POINTER(SynthBandConfig), C.c_uint32, i, C.POINTER(i), C.POINTER(SynthStation),
+                                    C.POINTER(SynthFrontend), C.c_int64, i, vp, vp, sz, i]),
+        "fmx_synth_band_create": (i, [vp, C.POINTER(SynthBandConfig), C.c_uint32, i, C.POINTER(i),
+                                      C.POINTER(SynthStation), C.POINTER(SynthFrontend), vp, C.POINTER(vp)]),
+        "fmx_synth_band_generate": (i, [vp, C.c_int64, i, vp, sz]),
+        "fmx_synth_band_destroy": (i, [vp]),
         "fmx_design_taps": (i, [C.POINTER(Config), i, fp, i]),
         "fmx_resamp_schedule": (i, [C.c_float, i, C.POINTER(C.c_int), fp, i]),
         "fmx_xdr_pi_reset": (None, [C.POINTER(XdrPiState)]),
@@ -805,6 +828,120 @@ def synth_host(scfg, ch0, n_ch, sample0, n_samples, bits=None, threads=8):
     if rc != FMX_OK:
         raise FmxError("fmx_synth_host failed")
     return out
+
+
+def make_synth_band(wide_rate=2_400_000, format=FMX_WB_S16, kind=2, seed_base=0xF00D, max_offset_hz=5000,
+                    rds_level=0.05, n_bits=4096, noise_std=0.0):
+    return SynthBandConfig(wide_rate, format, kind, seed_base, max_offset_hz, rds_level, n_bits, noise_std)
+
+
+def synth_band_tile():
+    """fmx_synth_band_tile: samples per workgroup of the band kernel."""
+    return lib().fmx_synth_band_tile()
+
+
+def synth_band_content(bcfg):
+    """fmx_synth_band_content: the SynthConfig whose channel ch0 + g is station g's content."""
+    out = SynthConfig()
+    if lib().fmx_synth_band_content(C.byref(bcfg), C.byref(out)) != FMX_OK:
+        raise FmxError(f"fmx_synth_band_content failed: {lib().fmx_synth_band_error().decode()}")
+    return out
+
+
+def _synth_band_tables(captures, frontends):
+    """captures: [[(freq_hz, amplitude), ...], ...]; frontends: None or one
+    (dc_i, dc_q, q_gain, q_cross) per capture -> the C tables."""
+    first = [0]
+    for c in captures:
+        first.append(first[-1] + len(c))
+    flat = [(int(f), float(a)) for c in captures for (f, a) in c]
+    t_first = (C.c_int * len(first))(*first)
+    t_st = (SynthStation * max(len(flat), 1))(*[SynthStation(f, a) for f, a in flat])
+    t_fe = None
+    if frontends is not None:
+        if len(frontends) != len(captures):
+            raise ValueError("one front end per capture")
+        t_fe = (SynthFrontend * max(len(frontends), 1))(*[SynthFrontend(*[float(v) for v in fe]) for fe in frontends])
+    return first, t_first, t_st, t_fe
+
+
+def synth_band_bits(bcfg, ch0, n_stations):
+    """The content config, the RDS bit rows [n_stations][n_bits] and the
+    transmitted groups [n_stations][n_bits // 104][4] of a band's stations
+    (fmx_synth_rds_bits on the content config); bits and groups are None
+    unless the band's kind is 2."""
+    content = synth_band_content(bcfg)
+    if bcfg.kind != 2 or bcfg.n_bits <= 0:
+        return content, None, None
+    bits, groups = synth_rds_bits(content, ch0, n_stations)
+    return content, bits, groups
+
+
+def synth_band_host(bcfg, ch0, captures, sample0, n_samples, frontends=None, bits="auto", wide_stride=None,
+                    threads=8, out=None):
+    """fmx_synth_band_host: the band on the CPU, [captures][wide_stride][2]
+    int16 or uint8.  bits: the RDS bit rows, None, or "auto" (made from the
+    content config when the kind is 2); out: an array to fill (cells past
+    n_samples of a row are left as they are)."""
+    import numpy as np
+    first, t_first, t_st, t_fe = _synth_band_tables(captures, frontends)
+    if isinstance(bits, str):
+        bits = synth_band_bits(bcfg, ch0, first[-1])[1]
+    stride = n_samples if wide_stride is None else wide_stride
+    if out is None:
+        out = np.zeros((len(captures), max(stride, 0), 2), dtype=np.int16 if bcfg.format == FMX_WB_S16 else np.uint8)
+    rc = lib().fmx_synth_band_host(C.byref(bcfg), ch0, len(captures), t_first, t_st, t_fe, sample0, n_samples,
+                                   bits.ctypes.data if bits is not None else None, out.ctypes.data, stride, threads)
+    if rc != FMX_OK:
+        raise FmxError(f"fmx_synth_band_host failed ({rc}): {lib().fmx_synth_band_error().decode()}")
+    return out
+
+
+class SynthBand:
+    """The synthetic FM band on the GPU (fmx_synth_band_*): len(captures) wide
+    captures of one rate and format, capture s with the stations captures[s],
+    a list (possibly empty) of (freq_hz, amplitude); station g of all has the
+    content of channel ch0 + g of .content.  .bits and .groups are the RDS bit
+    rows and the transmitted groups of a kind-2 band (else None).  generate
+    is one launch on the handle's stage stream.  Close it before its handle."""
+
+    def __init__(self, handle, cfg, ch0, captures, frontends=None):
+        self.L = lib()
+        self.handle = handle
+        self.cfg = cfg
+        self.ch0 = ch0
+        self.captures = len(captures)
+        self.b = None
+        self.first_station, t_first, t_st, t_fe = _synth_band_tables(captures, frontends)
+        self.n_stations = self.first_station[-1]
+        self.content, self.bits, self.groups = synth_band_bits(cfg, ch0, self.n_stations)
+        b = C.c_void_p()
+        rc = self.L.fmx_synth_band_create(handle.h, C.byref(cfg), ch0, self.captures, t_first, t_st, t_fe,
+                                          self.bits.ctypes.data if self.bits is not None else None, C.byref(b))
+        if rc != FMX_OK:
+            raise FmxError(f"fmx_synth_band_create failed ({rc}): {self.L.fmx_last_error(handle.h).decode()}")
+        self.b = b
+
+    def _ck(self, rc, what):
+        if rc != FMX_OK:
+            raise FmxError(f"{what} failed ({rc}): {self.L.fmx_last_error(self.handle.h).decode()}")
+
+    def close(self):
+        if self.b is not None and self.handle.h is not None:
+            self.L.fmx_synth_band_destroy(self.b)
+        self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def generate(self, sample0, n, d_out, wide_stride):
+        """d_out: [captures][wide_stride] interleaved I/Q samples of the band's
+        format; samples sample0 .. sample0 + n of every capture are written."""
+        self._ck(self.L.fmx_synth_band_generate(self.b, sample0, n, C.c_void_p(d_out), wide_stride),
+                 "fmx_synth_band_generate")
 
 
 def design_taps(cfg, which):

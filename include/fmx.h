@@ -47,7 +47,10 @@
 extern "C" {
 #endif
 
-/* ABI history: the bank scan's correction per capture (fmx_wb_bank_scan_set_iq_correction,
+/* ABI history: the synthetic FM band (fmx_synth_band_content, fmx_synth_band_tile, fmx_synth_band_host,
+ * fmx_synth_band_create, fmx_synth_band_generate, fmx_synth_band_destroy, and fmx_synth_band_error for the
+ * host calls' messages: wide captures of many stations, generated on the GPU) arrived at 13 without a bump:
+ * additions only; the bank scan's correction per capture (fmx_wb_bank_scan_set_iq_correction,
  * fmx_wb_bank_scan_iq_correction) arrived at 13 without a bump: additions only;
  * the band scan over a capture bank (fmx_wb_bank_scan_create, fmx_wb_bank_scan_destroy,
  * fmx_wb_bank_scan_set_signal_params, fmx_wb_bank_scan_reset, fmx_wb_bank_scan_process, fmx_wb_bank_scan_groups:
@@ -793,6 +796,79 @@ int fmx_synth_host(const fmx_synth_config *cfg, uint32_t ch0, int n_ch, int64_t 
 /* device generation on the handle's stream: d_out [n_ch][out_stride] */
 int fmx_synth_device(void *handle, const fmx_synth_config *cfg, uint32_t ch0, int n_ch, int64_t sample0,
                      int n_samples, const uint8_t *d_bits, uint8_t *d_out, size_t out_stride);
+
+/* ---- synthetic FM band: wide captures of many stations (fmx_synth_band.h) ----
+ * A band is n_captures captures of one rate wide_rate (any integer 480 000 ..
+ * 30 720 000 Hz) and one format (FMX_WB_U8 / FMX_WB_S16).  Capture s holds
+ * the stations [first_station[s], first_station[s + 1]): the table starts at 0
+ * and does not decrease (fmx_wb_bank_create's rules), an empty capture is
+ * legal (noise only); 1 <= n_captures <= 1024, 0 <= stations <= 8192 in all.
+ * Station g (global index) is an FM carrier of `amplitude` (finite, >= 0) at
+ * freq_hz from the capture's centre, |freq_hz| + max_offset_hz <= wide_rate / 2,
+ * with the content of channel ch0 + g of the generator above:
+ * fmx_synth_band_content writes that generator's config (iq_rate = wide_rate,
+ * amplitude 1, no noise, no level spread), and RDS bit row g is row g of
+ * fmx_synth_rds_bits(content, ch0, stations) (kind 2 needs 104 <= n_bits <= 2^24
+ * and the table).  The phase of every tone is a closed form of the absolute
+ * sample index i (0 <= sample0, sample0 + n_samples <= 2^40) through exact
+ * integer residues, and phase and station sum are in double, so a sample
+ * depends on (config, tables, capture, i) alone: the bytes do not depend on
+ * how a stream is cut into calls, on the grid, or on the run.  noise_std > 0
+ * adds white Gaussian noise per component, seeded by seed_base and the
+ * capture's index.  The front end of capture s (NULL table: the identity
+ * 0, 0, 1, 0; finite, q_gain > 0) then gives I' = I + dc_i and
+ * Q' = q_gain Q + q_cross I + dc_q, which fmx_wb_set_iq_correction(FIXED,
+ * {dc_i, dc_q, 1 / q_gain, -q_cross / q_gain}) inverts exactly.  Quantised
+ * with ties to even: u8 clamp(rint(127.5 v + 127.5), 0, 255), int16
+ * clamp(rint(32768 v), -32768, 32767), interleaved I, Q.
+ *
+ * Output is [n_captures][wide_stride] samples, wide_stride >= n_samples; cells
+ * past n_samples of a row are never written.  fmx_synth_band_host writes host
+ * memory on `threads` threads and needs no GPU.  fmx_synth_band_create
+ * validates, derives every station once and puts the tables into device
+ * memory; fmx_synth_band_generate is one launch queued on the handle's stage
+ * stream (the one fmx_wb_process is queued on), with no host synchronisation
+ * and no host-to-device copy, so a following channelizer call on the same
+ * handle needs no sync.  d_out needs the element's alignment only (2 bytes for
+ * int16, 1 for u8); an unaligned base takes narrower stores and gives
+ * identical bytes.  n_samples == 0 does nothing.
+ *
+ * Every refusal is FMX_E_INVALID with a message naming the function and the
+ * condition: in fmx_last_error of the handle for create / generate / destroy,
+ * and in fmx_synth_band_error (the calling thread's last refusal) for the two
+ * host calls.  A NULL object or handle returns it without touching a device.
+ * The object is a kind of its own: every other fmx_* call that takes an
+ * object refuses it, and these calls refuse every other object.
+ * host and device agree to 1 LSB (they differ by the ulps of sin / cos and of
+ * the noise's float functions, which can only move a value across a rounding
+ * tie).  These symbols arrived without a bump of FMX_ABI_VERSION (see above). */
+typedef struct {
+  int wide_rate, format, kind; /* kind: 0 mono two-tone, 1 stereo, 2 stereo + RDS */
+  uint32_t seed_base;
+  int max_offset_hz;
+  float rds_level;
+  int n_bits;
+  float noise_std;
+} fmx_synth_band_config;
+typedef struct {
+  int freq_hz;
+  float amplitude;
+} fmx_synth_station;
+typedef struct {
+  double dc_i, dc_q, q_gain, q_cross;
+} fmx_synth_frontend;
+int fmx_synth_band_content(const fmx_synth_band_config *cfg, fmx_synth_config *out); /* host only */
+int fmx_synth_band_tile(void); /* host only: samples per workgroup of the kernel */
+const char *fmx_synth_band_error(void); /* host only: the calling thread's last refusal by the two host calls */
+int fmx_synth_band_host(const fmx_synth_band_config *cfg, uint32_t ch0, int n_captures, const int *first_station,
+                        const fmx_synth_station *stations, const fmx_synth_frontend *frontends /* or NULL */,
+                        int64_t sample0, int n_samples, const uint8_t *h_bits /* [stations][n_bits] or NULL */,
+                        void *h_out, size_t wide_stride /* samples */, int threads);
+int fmx_synth_band_create(void *handle, const fmx_synth_band_config *cfg, uint32_t ch0, int n_captures,
+                          const int *first_station, const fmx_synth_station *stations,
+                          const fmx_synth_frontend *frontends /* or NULL */, const uint8_t *h_bits, void **band);
+int fmx_synth_band_generate(void *band, int64_t sample0, int n_samples, void *d_out, size_t wide_stride);
+int fmx_synth_band_destroy(void *band);
 
 /* ---- diagnostics (host only, no GPU needed) ---- */
 /* Filter taps the handle would use: which = 0 decimator, 1 IQ FIR,
